@@ -28,6 +28,14 @@ Default workload: c3 at N = 1 (the single-GPU roofline config), c4 at N > 1
 (BASELINE configs[3], the multi-GPU config).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c4|c5]
+                       [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result
+  line.  --full adds everything that takes runs of its own: the event-timed
+  pass of the residual+Jacobian kernel and the measured device copy (the
+  "roofline" record), and the CPU baseline (oracle/; --no-cpu-baseline leaves
+  it out, --cpu-seconds sizes it).
+  --dump-outputs DIR: after the timed steps rank 0 writes DIR/<name>.npy
+  (float64): what the last timed LM step computed, see dump_outputs().
   N > 1 either under a launcher (python -m torch.distributed.run
   --nproc-per-node N bench.py --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE set,
   WORLD_SIZE must equal N) or standalone: without WORLD_SIZE the process
@@ -244,12 +252,48 @@ def host_transport(rank: int, world: int):
     return allreduce
 
 
+DUMP_MAX_POINTS = 1_000_000   # rows of pts.npy (24 MB); larger shards: a fixed, seeded sample
+ITERATION_COLUMNS = ["iteration", "step_is_valid", "step_is_successful", "linear_solver_iterations", "cost",
+                     "cost_change", "gradient_max_norm", "gradient_norm", "step_norm", "relative_decrease",
+                     "trust_region_radius", "model_cost_change"]
+
+
+def dump_outputs(path, cams, pts, iteration_log):
+    """--dump-outputs: what a caller of the timed path receives, as float64
+    .npy files (at most ~40 MB), for comparing two builds output for output
+    (BA_HIP_LIB selects another build of the library):
+      cams.npy        [n_cams, 6]  the cameras ba_get_params returns
+      pts.npy         [n, 3]       the points; of more than DUMP_MAX_POINTS, the
+                                   rows pts_rows.npy names (seed 0, ascending)
+      pts_rows.npy    [n]          their row indices
+      iterations.npy  [k, 12]      the solve's ba_iteration records, columns
+                                   ITERATION_COLUMNS (every field but the time)
+    trajectory mode: of the timed solve itself.  fixed mode: the timed entry
+    point (ba_bench_iterations) hands back times only and leaves the step's
+    candidate on the device, so the arrays are those of the same LM step (same
+    x0, same radius, same options, same kernels) taken once more through
+    ba_solve with max_num_iterations = 1, after the timed region."""
+    import numpy as np
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    rows = np.arange(len(pts))
+    if len(pts) > DUMP_MAX_POINTS:
+        rows = np.sort(np.random.default_rng(0).choice(len(pts), DUMP_MAX_POINTS, replace=False))
+    np.save(out / "cams.npy", np.asarray(cams, np.float64))
+    np.save(out / "pts.npy", np.asarray(pts, np.float64)[rows])
+    np.save(out / "pts_rows.npy", rows.astype(np.float64))
+    np.save(out / "iterations.npy",
+            np.array([[float(r[c]) for c in ITERATION_COLUMNS] for r in iteration_log], np.float64)
+            .reshape(len(iteration_log), len(ITERATION_COLUMNS)))
+
+
 def dry_run_line(args, rank, world, local_rank, device):
     """BA_BENCH_DRYRUN=1 (CPU tests of the launch logic): what this rank would
     run, without any GPU call."""
     return json.dumps({"dry_run": True, "rank": rank, "world": world, "local_rank": local_rank, "device": device,
                        "workload": args.workload, "transport": args.transport, "steps": args.steps,
-                       "warmup": args.warmup, "mode": args.mode})
+                       "warmup": args.warmup, "mode": args.mode, "full": args.full,
+                       "dump_outputs": args.dump_outputs})
 
 
 def main():
@@ -267,8 +311,14 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0,
                     help="point-count scale of the problem (weak: of the per-GPU shard; strong: of the global "
                          "problem); 1 = the BASELINE size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target length of each CPU-baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the event-timed pass of the residual+Jacobian kernel "
+                         "and the measured device copy (roofline), and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes DIR/<name>.npy: what the last timed LM step computed")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="--full: target length of each CPU-baseline sample")
     ap.add_argument("--comm", action="store_true", help="use an RCCL communicator even at one rank (tests)")
     ap.add_argument("--linear-solver", default=None, choices=["dense", "iterative"],
                     help="DENSE_SCHUR (the reference's) or ITERATIVE_SCHUR (implicit Schur + PCG)")
@@ -404,10 +454,14 @@ def main():
                               "= the solve's wall time / its LM iterations, initial linearisation included"}
         steps_done = summ.num_iterations
         ms_dev = dt / max(steps_done, 1) * 1e3
-        # the r+J kernel's launch time does not depend on the radius: timed in
-        # a short fixed-radius pass after the solve
-        _, ms_rj = solver.bench_iterations(min(args.steps, 10), options=opts)
-        barrier()
+        if args.dump_outputs:   # the timed solve's own results
+            dump = solver.params() + (solver.iteration_log(),)
+        ms_rj = None
+        if args.full:
+            # the r+J kernel's launch time does not depend on the radius: timed in
+            # a short fixed-radius pass after the solve
+            _, ms_rj = solver.bench_iterations(min(args.steps, 10), options=opts)
+            barrier()
     else:
         # warmup (first call also computes the Jacobi scaling, as LM iteration 0 does)
         solver.bench_iterations(max(1, args.warmup), options=opts)
@@ -427,7 +481,18 @@ def main():
         # per-iteration host wall times of the timed region (the
         # median of >= 10 iterations after 2 warm-ups), reported beside the mean
         it_ms = solver.bench_iteration_times()
-        if not rj_in_loop:
+        if args.dump_outputs:
+            # the timed call hands back times only: the same LM step (x0, the
+            # same radius and options) once more through ba_solve, which
+            # returns what it computed (dump_outputs), then back to x0
+            import dataclasses
+            x0c, x0p = solver.problem.cams.copy(), solver.problem.pts.copy()
+            solver.solve(dataclasses.replace(opts, max_num_iterations=1, function_tolerance=0.0,
+                                             gradient_tolerance=0.0, parameter_tolerance=0.0))
+            dump = solver.params() + (solver.iteration_log(),)
+            solver.set_params(x0c, x0p)
+            barrier()
+        if args.full and not rj_in_loop:
             _, ms_rj = solver.bench_iterations(args.steps, options=opts)
             barrier()
 
@@ -447,50 +512,52 @@ def main():
     mixed = precision == "MIXED_FP32"
     N, Pn, Cn = float(problem.n_obs), float(problem.n_pts), float(problem.n_cams)
     B_rj = (96.0 * N + 12.0 * Pn + 24.0 * Cn) if mixed else (176.0 * N + 24.0 * Pn + 48.0 * Cn)
-    achieved = B_rj / (ms_rj * 1e-3) / 1e9
-    # J-free iteration (libba_hip's default, BA_JR unset): the timed kernel is
-    # k_lin_point, which forms r and J in registers and reduces them into the
-    # point blocks without storing J (camera table in LDS up to 200 cameras,
-    # the L2-resident global table beyond); SURVEY.md §8d prices such a fused
-    # kernel against the unfused B_rj, labelled "effective"
-    jrfree = os.environ.get("BA_JR") != "1"
-    kname = ("k_lin_point" if problem.n_cams <= 200 else "k_lin_point_d") if jrfree else "k_linearize"
-    pmc = pmc_record(cfg, kname, problem.n_obs, args.scale)
-    traffic = pmc["hbm_bytes_per_launch"] if pmc else None
-    # measured copy bandwidth of this GPU (reported beside the
-    # vendor peak, which stays the denominator of `frac`): 1 GiB non-temporal
-    # 16-B copy, 10 launches, after the timed region
-    copy_gbs = solver.stream_copy(1 << 30, 10)
-    roofline = {"kernel": (f"{kname} (residual + Jacobian + Huber + point blocks; J not materialised)" if jrfree
-                           else "k_linearize (residual+Jacobian)"),
-                "effective": jrfree,
-                "bound": "hbm", "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic, "algorithmic_bytes": B_rj,
-                "algorithmic_formula": ("96 N + 12 P + 24 C (fp32 r + J storage, SURVEY.md §8d)" if mixed
-                                        else "176 N + 24 P + 48 C (fp64 r + J, SURVEY.md §8d)"),
-                "avg_launch_ms": round(ms_rj, 5),
-                "timing": ("HIP events around every launch, in the timed region" if rj_in_loop else
-                           "HIP events around every launch, in a second pass of the same K LM iterations"
-                           if args.mode == "fixed" else
-                           "HIP events around every launch, in a fixed-radius pass after the trajectory"),
-                "measured_copy": round(copy_gbs, 1), "frac_of_copy": round(achieved / copy_gbs, 4)}
-    if jrfree:
-        roofline["effective_note"] = (
-            "J is never stored: the kernel moves far fewer bytes than the unfused B_rj it is priced against, so "
-            "'achieved' and 'frac_of_copy' (> 1 possible) are bookkeeping, not a bandwidth claim; the kernel's "
-            "real HBM rate is 'real'")
-    if pmc:
-        real = pmc["hbm_bytes_per_launch"] / (ms_rj * 1e-3) / 1e9
-        roofline["real"] = {"hbm_bytes_per_launch": pmc["hbm_bytes_per_launch"], "achieved": round(real, 1),
-                            "frac": round(real / HBM_PEAK_GBS, 4), "source": pmc["source"]}
-        if pmc.get("valu_insts_per_launch"):
-            # fp64 VALU issue: a wave64 fp64 instruction holds its SIMD's 16
-            # fp64 lanes 4 cycles; 4 SIMDs x 256 CUs at the 2.4 GHz peak clock
-            # (4 cycles per wave64 VALU instruction on a 16-lane SIMD)
-            busy = pmc["valu_insts_per_launch"] * 4.0 / (ms_rj * 1e-3 * 2.4e9 * 1024.0)
-            roofline["real"]["valu_insts_per_launch"] = pmc["valu_insts_per_launch"]
-            roofline["real"]["valu_busy_frac_est"] = round(busy, 4)
+    roofline = None   # the kernel line needs the event-timed pass and the measured copy: --full
+    if args.full:
+        achieved = B_rj / (ms_rj * 1e-3) / 1e9
+        # J-free iteration (libba_hip's default, BA_JR unset): the timed kernel is
+        # k_lin_point, which forms r and J in registers and reduces them into the
+        # point blocks without storing J (camera table in LDS up to 200 cameras,
+        # the L2-resident global table beyond); SURVEY.md §8d prices such a fused
+        # kernel against the unfused B_rj, labelled "effective"
+        jrfree = os.environ.get("BA_JR") != "1"
+        kname = ("k_lin_point" if problem.n_cams <= 200 else "k_lin_point_d") if jrfree else "k_linearize"
+        pmc = pmc_record(cfg, kname, problem.n_obs, args.scale)
+        traffic = pmc["hbm_bytes_per_launch"] if pmc else None
+        # measured copy bandwidth of this GPU (reported beside the
+        # vendor peak, which stays the denominator of `frac`): 1 GiB non-temporal
+        # 16-B copy, 10 launches, after the timed region
+        copy_gbs = solver.stream_copy(1 << 30, 10)
+        roofline = {"kernel": (f"{kname} (residual + Jacobian + Huber + point blocks; J not materialised)" if jrfree
+                               else "k_linearize (residual+Jacobian)"),
+                    "effective": jrfree,
+                    "bound": "hbm", "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": traffic, "algorithmic_bytes": B_rj,
+                    "algorithmic_formula": ("96 N + 12 P + 24 C (fp32 r + J storage, SURVEY.md §8d)" if mixed
+                                            else "176 N + 24 P + 48 C (fp64 r + J, SURVEY.md §8d)"),
+                    "avg_launch_ms": round(ms_rj, 5),
+                    "timing": ("HIP events around every launch, in the timed region" if rj_in_loop else
+                               "HIP events around every launch, in a second pass of the same K LM iterations"
+                               if args.mode == "fixed" else
+                               "HIP events around every launch, in a fixed-radius pass after the trajectory"),
+                    "measured_copy": round(copy_gbs, 1), "frac_of_copy": round(achieved / copy_gbs, 4)}
+        if jrfree:
+            roofline["effective_note"] = (
+                "J is never stored: the kernel moves far fewer bytes than the unfused B_rj it is priced against, so "
+                "'achieved' and 'frac_of_copy' (> 1 possible) are bookkeeping, not a bandwidth claim; the kernel's "
+                "real HBM rate is 'real'")
+        if pmc:
+            real = pmc["hbm_bytes_per_launch"] / (ms_rj * 1e-3) / 1e9
+            roofline["real"] = {"hbm_bytes_per_launch": pmc["hbm_bytes_per_launch"], "achieved": round(real, 1),
+                                "frac": round(real / HBM_PEAK_GBS, 4), "source": pmc["source"]}
+            if pmc.get("valu_insts_per_launch"):
+                # fp64 VALU issue: a wave64 fp64 instruction holds its SIMD's 16
+                # fp64 lanes 4 cycles; 4 SIMDs x 256 CUs at the 2.4 GHz peak clock
+                # (4 cycles per wave64 VALU instruction on a 16-lane SIMD)
+                busy = pmc["valu_insts_per_launch"] * 4.0 / (ms_rj * 1e-3 * 2.4e9 * 1024.0)
+                roofline["real"]["valu_insts_per_launch"] = pmc["valu_insts_per_launch"]
+                roofline["real"]["valu_busy_frac_est"] = round(busy, 4)
 
     # whole-iteration figure (reported beside the kernel line):
     # B_iter = 176N (r+J) + 160N (r, J re-read for assembly) + 144N (W write)
@@ -512,7 +579,9 @@ def main():
                                    "Infinity-Cache Schur gathers, not by HBM")}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *dump)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         if problem.n_obs <= 20_000_000:
             cpu = cpu_baseline_leg(problem, cfg, args.cpu_seconds, precision)
         else:   # one CPU LM iteration alone would take minutes: no bounded sample
@@ -560,7 +629,10 @@ def main():
             "iteration_roofline": iteration_roofline,
             "cpu_baseline": cpu,
             "mode": args.mode,
+            "full": args.full,
         }
+        if args.dump_outputs:
+            out["outputs"] = str(args.dump_outputs)
         if trajectory is not None:
             out["trajectory"] = trajectory
         print(json.dumps(out), file=json_out, flush=True)

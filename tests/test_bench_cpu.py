@@ -86,6 +86,48 @@ def test_strong_workload_needs_a_divisor_of_8():
     assert out.returncode != 0 and "dividing 8" in out.stderr
 
 
+def test_plain_run_is_lean_and_full_is_opt_in(tmp_path):
+    d = json.loads(_bench(["--gpus", "1", "--steps", "5"]).stdout)
+    assert d["full"] is False and d["dump_outputs"] is None and d["steps"] == 5
+    out = _bench(["--gpus", "1", "--full", "--dump-outputs", str(tmp_path / "o")])
+    assert out.returncode == 0, out.stderr
+    d = json.loads(out.stdout)
+    assert d["full"] is True and d["dump_outputs"] == str(tmp_path / "o")
+    out = _bench(["--gpus", "2", "--full"])            # the ranks get the parent's options
+    assert out.returncode == 0 and json.loads(out.stdout)["full"] is True
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: float64 .npy files; a shard of more than DUMP_MAX_POINTS
+    points is written as the same seeded sample every time."""
+    rng = np.random.default_rng(1)
+    cams, pts = rng.standard_normal((7, 6)), rng.standard_normal((50, 3))
+    log = [dict({c: 0.0 for c in bench.ITERATION_COLUMNS}, iteration=i, cost=2.5 - i, iteration_time_s=float(i))
+           for i in range(2)]
+    bench.dump_outputs(tmp_path / "a", cams, pts, log)
+    got = {f.stem: np.load(f) for f in sorted((tmp_path / "a").glob("*.npy"))}
+    assert sorted(got) == ["cams", "iterations", "pts", "pts_rows"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["cams"], cams) and np.array_equal(got["pts"], pts)
+    assert np.array_equal(got["pts_rows"], np.arange(50))
+    assert got["iterations"].shape == (2, len(bench.ITERATION_COLUMNS))
+    assert got["iterations"][:, bench.ITERATION_COLUMNS.index("cost")].tolist() == [2.5, 1.5]
+    assert "iteration_time_s" not in bench.ITERATION_COLUMNS      # times differ from run to run
+
+    old = bench.DUMP_MAX_POINTS
+    bench.DUMP_MAX_POINTS = 20
+    try:
+        bench.dump_outputs(tmp_path / "b", cams, pts, log)
+        bench.dump_outputs(tmp_path / "c", cams, pts, log)
+    finally:
+        bench.DUMP_MAX_POINTS = old
+    rows = np.load(tmp_path / "b" / "pts_rows.npy").astype(int)
+    assert len(rows) == 20 and len(set(rows)) == 20 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "pts.npy"), pts[rows])
+    for name in ("pts", "pts_rows"):
+        assert np.array_equal(np.load(tmp_path / "b" / f"{name}.npy"), np.load(tmp_path / "c" / f"{name}.npy"))
+
+
 def test_host_transport_pins_the_device():
     out = _bench(["--gpus", "2", "--transport", "host", "--device", "0"])
     assert out.returncode == 0, out.stderr

@@ -5,7 +5,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-timeout -k 10 900 python3 -u bench.py --config c4 --scale 1.0 --steps 3 --warmup 1 --cpu-seconds 20 \
+timeout -k 10 900 python3 -u bench.py --config c4 --scale 1.0 --steps 3 --warmup 1 --full --cpu-seconds 20 \
   > gpurun_out/c4full_dense.json 2> gpurun_out/c4full_dense.err || exit $?
 cat gpurun_out/c4full_dense.json
 timeout -k 10 600 python3 -u bench.py --config c4 --scale 1.0 --steps 3 --warmup 1 --linear-solver iterative \

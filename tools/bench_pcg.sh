@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 OUT=gpurun_out
 run() {  # name, args...
   local name=$1; shift
-  timeout -k 10 ${TLIM:-400} python3 -u bench.py --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err
+  timeout -k 10 ${TLIM:-400} python3 -u bench.py --full --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err
   local rc=$?; cat $OUT/$name.json; tail -2 $OUT/$name.err; return $rc
 }
 run pcg_c3 --steps 10 --warmup 2 --linear-solver iterative &&

@@ -8,7 +8,8 @@
 # space inside bench / pytest arguments:
 #   tests[:EXPR]               pytest -m gpu [-k EXPR] (e.g. tests:blocks+or+persistent)
 #   smoke                      __graft_entry__.smoke()
-#   bench:TAG[:ARGS]           python bench.py ARGS > OUTDIR/bench_TAG.json
+#   bench:TAG[:ARGS]           python bench.py ARGS > OUTDIR/bench_TAG.json (ARGS with --full:
+#                              the kernel roofline and the CPU baseline too)
 #   prof:TAG[:ARGS]            rocprofv3 --kernel-trace --stats of bench.py ARGS
 #                              (summary: OUTDIR/prof_TAG/.../kernel_stats.csv)
 #   hbm:TAG[:ARGS]             FETCH_SIZE and WRITE_SIZE passes (separate, as the
