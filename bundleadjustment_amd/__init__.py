@@ -7,7 +7,8 @@ ctypes binding, problem container, synthetic problem generator, and the
 optimizer classes that mirror the reference's API (Optimizer.h:196-289).
 """
 from .problem import Problem, make_config, make_synthetic, shard_points, HUBER_A  # noqa: F401
+from ._native import BAError  # noqa: F401
 from .solver import Options, Solver, Summary, solve  # noqa: F401
 
 __all__ = ["Problem", "make_config", "make_synthetic", "shard_points", "HUBER_A", "Options", "Solver", "Summary",
-           "solve"]
+           "solve", "BAError"]

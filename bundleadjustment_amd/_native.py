@@ -15,7 +15,7 @@ LIB_PATH = PKG_DIR / "libba_hip.so"
 BA_OK = 0
 BA_ABI_VERSION = 2          # include/ba_hip.h
 STATUS_NAMES = {0: "BA_OK", 1: "BA_ERR_INVALID_ARGUMENT", 2: "BA_ERR_DEVICE", 3: "BA_ERR_OUT_OF_MEMORY",
-                4: "BA_ERR_NO_PROBLEM", 5: "BA_ERR_COMM"}
+                4: "BA_ERR_NO_PROBLEM", 5: "BA_ERR_COMM", 6: "BA_ERR_SINGULAR"}
 TERMINATION_NAMES = {0: "CONVERGENCE", 1: "NO_CONVERGENCE", 2: "FAILURE"}
 
 
@@ -85,6 +85,13 @@ class ba_pose_batch(C.Structure):
     ]
 
 
+class ba_covariance_request(C.Structure):
+    _fields_ = [
+        ("n_cam_pairs", C.c_int32), ("n_points", C.c_int32), ("cam_pairs", C.c_void_p), ("cam_cov", C.c_void_p),
+        ("points", C.c_void_p), ("pt_cov", C.c_void_p),
+    ]
+
+
 # int (*)(void* user, double* values, int64_t n, int op) of ba_comm_init_host
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int)
 
@@ -115,6 +122,8 @@ SIGNATURES = [
     ("ba_prune", C.c_int, [C.c_void_p, C.POINTER(ba_prune_problem), C.c_void_p]),
     ("ba_solve_pose_batch", C.c_int, [C.c_void_p, C.POINTER(ba_pose_batch), C.POINTER(ba_options), C.c_void_p,
                                       C.POINTER(ba_summary)]),
+    ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
+    ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("ba_synchronize", C.c_int, [C.c_void_p]),
     ("ba_bench_iterations", C.c_int, [C.c_void_p, C.POINTER(ba_options), C.c_int, C.c_double,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -240,6 +240,15 @@ int chol_persist_capacity(int device);   // resident k_chol_persist workgroups (
 // (pass_only, diagnostics: S formed by that launch's work items, nothing factored)
 void launch_cholesky_solve_ov(const DevProblem& P, const DevWork& W, OvPlan& plan, double radius, int epoch,
                               hipStream_t s, bool pass_only = false);
+// ba_cov.hip (ba_covariance), after a factorisation of the undamped reduced
+// system: U = L^-T into W.S, then Sigma_scaled = S_scaled^-1 into the lower
+// block tiles of W.Lf (the caller zeroes W.S afterwards)
+void launch_cov_inverse(const DevProblem& P, const DevWork& W, hipStream_t s);
+// pairs: compact variable-camera indices (-1: constant camera, a zero block); out [npairs][36]
+void launch_cov_cam_blocks(const DevProblem& P, const DevWork& W, const int2* pairs, int npairs, double* out,
+                           hipStream_t s);
+// pts: point indices; out [npts][9] (zeros for a constant point)
+void launch_cov_points(const DevProblem& P, const DevWork& W, const int* pts, int npts, double* out, hipStream_t s);
 bool obs_w_pc_ok(const DevProblem& P, const DevWork& W);   // k_obs_w_rc has the PCG record form for this source
 bool chol_persist_fits(int device, int n);   // every workgroup of k_chol_persist resident at once
 void chol_split_tasks(int n, std::vector<int4>& tasks, std::vector<int>& off);   // the split form's task table

@@ -86,7 +86,7 @@ struct ba_ctx {
   std::vector<int> perm;         // sorted obs -> caller obs
   std::vector<int> chol_off;     // split Cholesky task table: host step offsets (W.ctask_off)
   std::vector<int> cam_of_vc;
-  std::vector<uint8_t> cam_fixed_h;
+  std::vector<uint8_t> cam_fixed_h, pt_fixed_h;
   double huber_a = 0.0;
   DevProblem P{};
   DevWork W{};
@@ -135,6 +135,7 @@ struct ba_ctx {
   // solver state
   std::vector<ba_iteration> log;
   std::vector<double> bench_ms;   // host wall time of each iteration of the last ba_bench_iterations
+  std::vector<double> cov_ms;     // device time of the phases of the last ba_covariance
   bool scale_valid = false;
   double t_lin = 0.0, t_solve = 0.0;
 
@@ -455,6 +456,7 @@ void set_problem(ba_ctx* ctx, const ba_problem* pb) {
   ctx->h_obs_cam.swap(obs_cam);
   ctx->h_vc.swap(vc);
   ctx->h_pt_var.swap(pt_var);
+  ctx->pt_fixed_h.swap(pt_fixed);
   ctx->have_problem = true;
 }
 
@@ -1332,6 +1334,124 @@ void get_params(ba_ctx* ctx, double* cams, double* pts) {
   if (pts && ctx->np) HIP_OK(hipMemcpy(pts, ctx->W.pts, 3 * sizeof(double) * ctx->np, hipMemcpyDeviceToHost));
 }
 
+// ---------------------------------------------------------------------------
+// ceres::Covariance (defaults) for camera x camera and point x point blocks:
+// the undamped reduced system through a DENSE_SCHUR step's own passes and
+// factorisation, then ba_cov.hip
+// ---------------------------------------------------------------------------
+void covariance(ba_ctx* ctx, const ba_covariance_request* req) {
+  if (!req) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: request is NULL"};
+  if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, "ba_covariance before ba_set_problem"};
+  if (ctx->has_comm())
+    throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: not available on a context with a communicator"};
+  const int m = req->n_cam_pairs, k = req->n_points;
+  if (m < 0 || k < 0 || (m > 0 && (!req->cam_pairs || !req->cam_cov)) || (k > 0 && (!req->points || !req->pt_cov)))
+    throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: bad sizes or missing array"};
+  std::vector<int2> pairs_h(m);
+  for (int q = 0; q < m; ++q) {
+    int v[2];
+    for (int h = 0; h < 2; ++h) {
+      const int c = req->cam_pairs[2 * q + h];
+      if (c < 0 || c >= ctx->nc)
+        throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: camera index " + std::to_string(c) + " out of range"};
+      v[h] = ctx->h_vc[c];
+      if (v[h] < 0 && !ctx->cam_fixed_h[c])
+        throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: camera " + std::to_string(c) +
+                                                   " is variable but has no observation"};
+    }
+    pairs_h[q] = make_int2(v[0], v[1]);
+  }
+  for (int q = 0; q < k; ++q) {
+    const int p = req->points[q];
+    if (p < 0 || p >= ctx->np)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: point index " + std::to_string(p) + " out of range"};
+    if (!ctx->h_pt_var[p] && !ctx->pt_fixed_h[p])
+      throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: point " + std::to_string(p) +
+                                                 " is variable but has no observation"};
+  }
+  HIP_OK(hipSetDevice(ctx->device));
+  ba_options o;
+  ba_default_options(&o);   // DENSE_SCHUR, fp64
+  ctx->read_env();
+  const hipStream_t s = ctx->stream;
+  struct Events {
+    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  } ev;
+  for (hipEvent_t& x : ev.e) HIP_OK(hipEventCreate(&x));
+  HIP_OK(hipEventRecord(ev.e[0], s));
+  const LinResult L = linearize(ctx, true, o.min_lm_diagonal, o.max_lm_diagonal);
+  if (!L.ok) throw BaError{BA_ERR_SINGULAR, "ba_covariance: the linearisation is not finite"};
+  step_w_storage(ctx, o);
+  // an infinite radius: every D = sqrt(diag / radius) of the LM diagonal is
+  // exactly zero, so the step's passes form the undamped system
+  const double radius = std::numeric_limits<double>::infinity();
+  DevWork& W = ctx->W;
+  for (int attempt = 0;; ++attempt) {
+    form_reduced_dense(ctx, radius, false);   // (ensure_dense refuses a system too large for DENSE_SCHUR)
+    HIP_OK(hipEventRecord(ev.e[1], s));
+    launch_cholesky_solve2(ctx->P, W, ++ctx->chol_epoch, s);
+    HIP_OK(hipEventRecord(ev.e[2], s));
+    launch_reduce(W, bit(SL_ELIM_BAD), 0, s);
+    ctx->read_scalars();
+    const double* h = ctx->h_scal;
+    if (ctx->n > 0 && h[SL_CHOL_SPIN] != 0.0) {
+      // a hand-off of the factorisation never came: as in solve(), once more
+      // with the per-step launches (kept for this context)
+      if (attempt > 0 || (!W.chol_persist && !W.chol_fuse && !W.chol_flow))
+        throw BaError{BA_ERR_DEVICE, "dense Cholesky: a hand-off spin bound was hit"};
+      W.chol_persist = W.chol_flow = W.chol_fuse = false;
+      continue;
+    }
+    if (h[SL_ELIM_BAD] != 0.0)
+      throw BaError{BA_ERR_SINGULAR, "ba_covariance: " + std::to_string((long long)h[SL_ELIM_BAD]) +
+                                         " point block(s) not positive definite"};
+    if (ctx->n > 0 && h[SL_CHOL_BAD] != 0.0)
+      throw BaError{BA_ERR_SINGULAR, "ba_covariance: the reduced camera system is not positive definite"};
+    break;
+  }
+  // request and result staging (freed on every exit)
+  struct Dev {
+    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Dev() { for (void* x : p) if (x) (void)hipFree(x); }
+  } d;
+  if (m > 0) {
+    HIP_OK(hipMalloc(&d.p[0], sizeof(int2) * (size_t)m));
+    HIP_OK(hipMalloc(&d.p[1], sizeof(double) * 36 * (size_t)m));
+    HIP_OK(hipMemcpyAsync(d.p[0], pairs_h.data(), sizeof(int2) * (size_t)m, hipMemcpyHostToDevice, s));
+  }
+  if (k > 0) {
+    HIP_OK(hipMalloc(&d.p[2], sizeof(int) * (size_t)k));
+    HIP_OK(hipMalloc(&d.p[3], sizeof(double) * 9 * (size_t)k));
+    HIP_OK(hipMemcpyAsync(d.p[2], req->points, sizeof(int) * (size_t)k, hipMemcpyHostToDevice, s));
+  }
+  launch_cov_inverse(ctx->P, W, s);
+  HIP_OK(hipEventRecord(ev.e[3], s));
+  launch_cov_cam_blocks(ctx->P, W, static_cast<const int2*>(d.p[0]), m, static_cast<double*>(d.p[1]), s);
+  launch_cov_points(ctx->P, W, static_cast<const int*>(d.p[2]), k, static_cast<double*>(d.p[3]), s);
+  HIP_OK(hipGetLastError());
+  if (m > 0) HIP_OK(hipMemcpyAsync(req->cam_cov, d.p[1], sizeof(double) * 36 * (size_t)m, hipMemcpyDeviceToHost, s));
+  if (k > 0) HIP_OK(hipMemcpyAsync(req->pt_cov, d.p[3], sizeof(double) * 9 * (size_t)k, hipMemcpyDeviceToHost, s));
+  // W.S held L^-T: back to zeros, its state before the first step (the
+  // steps rewrite its lower triangle only)
+  if (ctx->n > 0) HIP_OK(hipMemsetAsync(W.S, 0, sizeof(double) * (size_t)(ctx->n + 1) * std::max(ctx->ld, 1), s));
+  HIP_OK(hipEventRecord(ev.e[4], s));
+  HIP_OK(hipStreamSynchronize(s));
+  for (size_t i = 0; i < 36 * (size_t)m; ++i)
+    if (!std::isfinite(req->cam_cov[i]))
+      throw BaError{BA_ERR_SINGULAR, "ba_covariance: camera block " + std::to_string(i / 36) + " is not finite"};
+  for (size_t i = 0; i < 9 * (size_t)k; ++i)
+    if (!std::isfinite(req->pt_cov[i]))
+      throw BaError{BA_ERR_SINGULAR, "ba_covariance: the block of point " + std::to_string(req->points[i / 9]) +
+                                         " is not finite"};
+  ctx->cov_ms.assign(4, 0.0);
+  for (int i = 0; i < 4; ++i) {
+    float ms = 0.0f;
+    HIP_OK(hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
+    ctx->cov_ms[i] = ms;
+  }
+}
+
 }  // namespace
 
 // ============================================================================
@@ -1735,6 +1855,18 @@ int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double*
     }
     if (n_out) *n_out = n;
   });
+}
+
+int ba_covariance(ba_ctx* ctx, const ba_covariance_request* req) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { covariance(ctx, req); });
+}
+
+int ba_covariance_times(ba_ctx* ctx, double* ms, int n) {
+  if (!ctx) return -BA_ERR_INVALID_ARGUMENT;
+  const int m = (int)ctx->cov_ms.size();
+  for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = ctx->cov_ms[i];
+  return m;
 }
 
 int ba_synchronize(ba_ctx* ctx) {

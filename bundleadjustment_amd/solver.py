@@ -223,6 +223,36 @@ class Solver:
                                              C.byref(n)), "ba_debug_blocks")
         return {"Hpp": Hpp, "gp": gp, "Hcc": Hcc, "gc": gc, "S": S, "rhs": rhs, "n": n.value}
 
+    def covariance(self, cam_pairs=None, points=None) -> tuple[np.ndarray, np.ndarray]:
+        """Marginal covariances at the current parameters (ba_covariance:
+        ceres::Covariance with its defaults, (J^T J)^-1 over the variable
+        blocks, no damping).  cam_pairs [m, 2]: camera index pairs (i, j), any
+        order; None: every (i, i).  points [k]: point indices; None: none.
+        Returns (cam_cov [m, 6, 6] with cam_cov[q] = Cov(cam_i, cam_j),
+        pt_cov [k, 3, 3]); blocks of constant cameras / points are zero.
+        Raises BAError (BA_ERR_SINGULAR when the system is not positive
+        definite: the caller must have removed the gauge)."""
+        if cam_pairs is None:
+            i = np.arange(self.problem.n_cams, dtype=np.int32)
+            cam_pairs = np.stack([i, i], axis=1)
+        cp = np.ascontiguousarray(cam_pairs, dtype=np.int32).reshape(-1, 2)
+        pt = np.ascontiguousarray(points if points is not None else [], dtype=np.int32).reshape(-1)
+        cam_cov = np.empty((cp.shape[0], 6, 6))
+        pt_cov = np.empty((pt.size, 3, 3))
+        req = N.ba_covariance_request(n_cam_pairs=cp.shape[0], n_points=pt.size, cam_pairs=_ptr(cp),
+                                      cam_cov=_ptr(cam_cov), points=_ptr(pt), pt_cov=_ptr(pt_cov))
+        self._check(self.lib.ba_covariance(self.h, C.byref(req)), "ba_covariance")
+        return cam_cov, pt_cov
+
+    def covariance_times(self) -> np.ndarray:
+        """Device time (ms) of the phases of the last covariance() call:
+        linearisation + reduced system, factorisation, inverse, gathers."""
+        n = self.lib.ba_covariance_times(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            self.lib.ba_covariance_times(self.h, _ptr(out), n)
+        return out
+
     def prune(self, extr, cam_center, K, obs_cam, obs_X, obs_uv, obs_inv_sigma, obs_dist) -> np.ndarray:
         """pruneCorrespondences (Optimizer.cpp:6-79) on the device for a batch of
         (keyframe, keypoint) pairs; returns a uint8 ba_prune_result per pair."""

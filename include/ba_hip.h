@@ -52,7 +52,8 @@ enum ba_status {
   BA_ERR_DEVICE = 2,          /* HIP runtime / kernel failure */
   BA_ERR_OUT_OF_MEMORY = 3,
   BA_ERR_NO_PROBLEM = 4,      /* ba_solve before ba_set_problem */
-  BA_ERR_COMM = 5             /* RCCL failure */
+  BA_ERR_COMM = 5,            /* RCCL failure */
+  BA_ERR_SINGULAR = 6         /* ba_covariance: the system is not positive definite */
 };
 
 enum ba_termination {          /* ceres::TerminationType subset */
@@ -293,6 +294,59 @@ int ba_solve_pose_batch(ba_ctx* ctx, const ba_pose_batch* batch, const ba_option
  * index (Jacobi-scaled columns, as Ceres' DENSE_SCHUR forms them). */
 int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double* Hcc, double* gc, double* S,
                     double* rhs, int* n_out);
+
+/* Marginal covariances of parameter blocks at the current parameters:
+ * ceres::Covariance with its defaults.  The covariance is (J^T J)^-1 with J
+ * the Huber-corrected Jacobian ba_linearize returns, taken over the variable
+ * blocks in unscaled parameters: no LM damping, no residual-variance factor.
+ * With H = J^T J = [[Hcc, Hcp], [Hpc, Hpp]]:
+ *   cameras  Sigma_cc = (Hcc - Hcp Hpp^-1 Hpc)^-1; cam_cov block q is the
+ *            6x6 Cov(cam_i, cam_j) of pair q = (i, j),
+ *   point p  Hpp_p^-1 + Hpp_p^-1 (sum_{a,b in obs(p)} Hpc_a Sigma[c(a), c(b)]
+ *            Hcp_b) Hpp_p^-1, 3x3.
+ * Every block of a constant camera or constant point is all zeros, as in
+ * Ceres.  Camera-point cross blocks are not available.
+ *
+ * The call linearises at the current parameters (with that linearisation's
+ * Jacobi scaling), forms and factors the undamped DENSE_SCHUR reduced system,
+ * inverts the factor on the device and gathers the requested blocks; it
+ * blocks until they are on the host.  It leaves the parameters unchanged, and
+ * a later ba_solve on the context is bit for bit what it would have been
+ * without the call.  Two calls at the same parameters give bitwise equal
+ * output.
+ *
+ * The caller must remove the gauge: the covariance exists only where J has
+ * full column rank.  With only one camera constant a monocular problem keeps
+ * its scale freedom (the reduced system's condition number is then ~1e17), so
+ * at least two cameras, or a camera and some points, must be constant.  A
+ * nearly singular system may still factor; the call then returns large
+ * finite values, not an error.
+ *
+ * Errors (the context stays usable after each):
+ *   BA_ERR_NO_PROBLEM        before ba_set_problem,
+ *   BA_ERR_INVALID_ARGUMENT  an index out of range; a requested block that
+ *                            is variable but has no observation (the message
+ *                            names it); a context with a communicator
+ *                            (ba_comm_init / ba_comm_init_host); a system too
+ *                            large for DENSE_SCHUR,
+ *   BA_ERR_SINGULAR          a point block or the reduced system is not
+ *                            positive definite, or a requested entry is not
+ *                            finite. */
+typedef struct {
+  int32_t n_cam_pairs, n_points;
+  const int32_t* cam_pairs;  /* [2*n_cam_pairs] caller camera indices (i, j), any order, i == j allowed */
+  double*        cam_cov;    /* [36*n_cam_pairs] row-major 6x6 Cov(cam_i, cam_j) */
+  const int32_t* points;     /* [n_points] caller point indices */
+  double*        pt_cov;     /* [9*n_points] row-major 3x3 */
+} ba_covariance_request;
+int ba_covariance(ba_ctx* ctx, const ba_covariance_request* req);
+
+/* Device time (ms, HIP events) of the phases of the last successful
+ * ba_covariance: [0] linearisation + reduced system, [1] factorisation (the
+ * launches of a DENSE_SCHUR step's), [2] inverse of the factor and
+ * Sigma = L^-T L^-1, [3] block gathers and the copies to the host.  Copies
+ * min(n, 4) values, returns 4 (0 before the first call).  Diagnostic. */
+int ba_covariance_times(ba_ctx* ctx, double* ms, int n);
 
 /* Blocks until all device work of the context is done. */
 int ba_synchronize(ba_ctx* ctx);

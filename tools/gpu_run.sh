@@ -16,6 +16,7 @@
 #                              guide prescribes), summarised by tools/pmc_summary.py
 #   sq:TAG[:ARGS]              one SQ / LDS counter pass, tools/pmc_table.py
 #   chol:N[:BIN[:TAG]]         tools/chol_bench_ns (or BIN) at order N (output file tagged TAG)
+#   cov:CONFIG[:ARGS]          tools/cov_bench.py --config CONFIG (c3 | c4shard) -> OUTDIR/cov_bench_CONFIG.json
 #   env:VAR=VALUE              exported for the following steps
 #   unset:VAR                  unexported
 # Every GPU step has its own time limit; a step that faults, aborts or times
@@ -84,6 +85,10 @@ for step in "$@"; do
       cf="$OUT/chol_$(basename "$bin")_$a1${a3:+_$a3}.txt"
       timeout -k 5 180 "$bin" "$a1" > "$cf" 2>&1
       rc=$?; grep -E "factor (flow|streamed)|differing|residual" "$cf" | tail -5 ;;
+    cov)
+      timeout -k 10 $T_BENCH python3 -u tools/cov_bench.py --config "$a1" --out "$OUT/cov_bench_$a1.json" ${a2//+/ } \
+        > "$OUT/cov_bench_$a1.log" 2>&1
+      rc=$?; tail -1 "$OUT/cov_bench_$a1.log" ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
   echo "$step rc=$rc"
