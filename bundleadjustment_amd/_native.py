@@ -85,6 +85,19 @@ class ba_pose_batch(C.Structure):
     ]
 
 
+BA_WINDOW_MAX_CAMS = 16     # include/ba_hip.h
+
+
+class ba_window_batch(C.Structure):
+    _fields_ = [
+        ("n_problems", C.c_int32), ("reserved", C.c_int32),
+        ("cam_offset", C.c_void_p), ("pt_offset", C.c_void_p), ("obs_offset", C.c_void_p),
+        ("cams", C.c_void_p), ("cam_fixed", C.c_void_p), ("cam_fixed_extr", C.c_void_p), ("K", C.c_void_p),
+        ("pts", C.c_void_p), ("pt_fixed", C.c_void_p), ("obs_cam", C.c_void_p), ("obs_pt", C.c_void_p),
+        ("obs_uv", C.c_void_p), ("huber_a", C.c_double),
+    ]
+
+
 class ba_covariance_request(C.Structure):
     _fields_ = [
         ("n_cam_pairs", C.c_int32), ("n_points", C.c_int32), ("cam_pairs", C.c_void_p), ("cam_cov", C.c_void_p),
@@ -122,6 +135,10 @@ SIGNATURES = [
     ("ba_prune", C.c_int, [C.c_void_p, C.POINTER(ba_prune_problem), C.c_void_p]),
     ("ba_solve_pose_batch", C.c_int, [C.c_void_p, C.POINTER(ba_pose_batch), C.POINTER(ba_options), C.c_void_p,
                                       C.POINTER(ba_summary)]),
+    ("ba_solve_window_batch", C.c_int, [C.c_void_p, C.POINTER(ba_window_batch), C.POINTER(ba_options), C.c_void_p,
+                                        C.c_void_p, C.POINTER(ba_summary)]),
+    ("ba_get_window_iteration_log", C.c_int, [C.c_void_p, C.c_int, C.POINTER(ba_iteration), C.c_int]),
+    ("ba_window_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("ba_synchronize", C.c_int, [C.c_void_p]),

@@ -279,6 +279,56 @@ void launch_pose_batch(int nprob, const int* off, const double* cams_in, const f
                        const float2* uv, double huber_a, const PoseOpts& o, double* cams_out, double* summ,
                        hipStream_t s);
 
+// batched small-window LM (cameras and points, DENSE_SCHUR), one workgroup
+// per problem (ba_window.hip).  All index arrays are local to their problem;
+// observations sorted by (point, camera).
+constexpr int kWinMaxCams = 16;    // = BA_WINDOW_MAX_CAMS: variable observed cameras per problem
+// doubles per camera table row, value-only camera record and observation
+// record of the scratch (= kTblRec, kRecL, kJR of the device headers)
+constexpr int kWinTbl = 42, kWinVRec = 48, kWinJR = 20;
+struct WinProb {
+  int cam0, pt0, obs0;             // first camera / point / observation of the problem in the concatenated arrays
+  int nc, np, no, nvc;
+  int vc0;                         // first compact variable camera (sum of nvc of the problems before)
+  int poff0;                       // pt_off + poff0: [np + 1] CSR of the observations by point
+  int coff0;                       // cam_off + coff0: [nvc + 1] CSR of cam_obs by compact variable camera
+  int vobs0;                       // cam_obs + vobs0: observations of variable cameras, grouped by camera
+  int pad;
+};
+struct WinArgs {
+  const WinProb* prob;
+  size_t NC, NP, NO, NV;           // totals over the batch (strides of the double-buffered scratch)
+  int log_cap;                     // ba_iteration records per problem
+  double huber_a;
+  // inputs
+  const double* cams_in; const double* pts_in;
+  const float* K; const float* extr;
+  const int* cam_vc;               // [NC] compact variable-camera index, -1: constant or unobserved
+  const uint8_t* pt_var;           // [NP] 1 = variable point with >= 1 residual
+  const int* pt_off; const int* obs_cam;
+  const int* obs_slot;             // [NO] cam_vc of the observation's camera if it is the first of its
+                                   //      (point, camera) group and the point is variable, else -1
+  const float2* uv;
+  const int* cam_off; const int* cam_obs;
+  // scratch ([2]: the state at x and at the candidate x')
+  double* pts;                     // [2][NP][3]
+  double* ctab;                    // [2][NC][kTblRec] K-folded camera tables
+  double* vrec;                    // [NC][48] value-only camera records at x'
+  double* JR;                      // [2][NO][20]
+  double* Hp;                      // [2][NP][9] Hpp (xx xy xz yy yz zz), gp
+  double* scale_p;                 // [NP][3]
+  double* prec;                    // [NP][9] L_p^-1 (00 10 11 20 21 22), u_p
+  double* Wb;                      // [NO][18] W = E L_p^-T of a (point, camera) group, at its first observation
+  double* hc;                      // [2][NV][27] Hcc (lower 21), gc
+  // outputs
+  double* cams_out; double* pts_out;
+  double* summ;                    // [nprob][8]: initial cost, final cost, iterations, successful, unsuccessful,
+                                   //             termination, log records, 0
+  void* log;                       // [nprob][log_cap] ba_iteration
+};
+size_t window_lds_bytes(int nvc);  // dynamic LDS of a problem with nvc variable observed cameras
+int launch_window_batch(int nprob, const WinArgs& A, const PoseOpts& o, size_t lds_bytes, hipStream_t s);   // hipError_t
+
 int grid_for(int n);
 int pt_group_grid(int np);   // grid of the kPtLanes-lanes-per-point kernels
 

@@ -100,6 +100,15 @@ struct ba_ctx {
   char* pose_buf = nullptr;      // ba_solve_pose_batch device staging (grown on demand)
   size_t pose_cap = 0;
   std::vector<char> pose_host;
+  // ba_solve_window_batch: device staging + scratch (grown on demand, reused
+  // across calls), the host copy of its inputs / outputs, the last call's logs
+  char* win_buf = nullptr;
+  size_t win_cap = 0;
+  std::vector<char> win_host;
+  std::vector<ba_iteration> win_log;   // [n_problems][win_log_cap]
+  std::vector<int> win_log_n;
+  int win_log_cap = 0;
+  std::vector<double> win_ms;          // ba_window_times of the last call
 
   // host copies of the sorted structure, kept for the lazily built
   // linear-solver structures (Schur pair lists / PCG duplicate pairs)
@@ -1522,6 +1531,7 @@ int ba_destroy(ba_ctx* ctx) {
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
   if (ctx->pose_buf) (void)hipFree(ctx->pose_buf);
+  if (ctx->win_buf) (void)hipFree(ctx->win_buf);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -1797,6 +1807,234 @@ int ba_solve_pose_batch(ba_ctx* ctx, const ba_pose_batch* b, const ba_options* o
       }
     }
   });
+}
+
+// ---------------------------------------------------------------------------
+// ba_solve_window_batch: host side.  Per problem: validate, find the variable
+// observed cameras (compact columns in increasing camera index) and the
+// variable points, sort the observations by (point, camera) as set_problem
+// does, build the point CSR, the (point, camera) group heads and the camera
+// CSR; one upload, one launch (ba_window.hip), one download.
+// ---------------------------------------------------------------------------
+int ba_solve_window_batch(ba_ctx* ctx, const ba_window_batch* b, const ba_options* opt, double* cams_out,
+                          double* pts_out, ba_summary* summaries) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_solve_window_batch: ";
+    if (!b || b->n_problems < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "bad batch"};
+    ba_options o;
+    if (opt) o = *opt; else ba_default_options(&o);
+    if (o.linear_solver != BA_DENSE_SCHUR) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "linear_solver must be BA_DENSE_SCHUR"};
+    if (o.precision != BA_FP64) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "precision must be BA_FP64"};
+    const int n = b->n_problems;
+    if (n > 0 && (!b->cam_offset || !b->pt_offset || !b->obs_offset)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null offset array"};
+    if (n > 0 && (b->cam_offset[0] != 0 || b->pt_offset[0] != 0 || b->obs_offset[0] != 0))
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "offset[0] != 0"};
+    for (int i = 0; i < n; ++i)
+      if (b->cam_offset[i + 1] < b->cam_offset[i] || b->pt_offset[i + 1] < b->pt_offset[i] ||
+          b->obs_offset[i + 1] < b->obs_offset[i])
+        throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "an offset array decreases at problem " + std::to_string(i)};
+    const size_t NC = n ? b->cam_offset[n] : 0, NP = n ? b->pt_offset[n] : 0, NO = n ? b->obs_offset[n] : 0;
+    if ((NC && (!b->cams || !b->K || !cams_out)) || (NP && (!b->pts || !pts_out)) ||
+        (NO && (!b->obs_cam || !b->obs_pt || !b->obs_uv)))
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null array"};
+    const double t0 = now_s();
+    // ---- structure
+    std::vector<WinProb> prob(n);
+    std::vector<int> cam_vc(NC, -1), pt_off(NP + n, 0), obs_cam(NO), obs_slot(NO, -1), cam_off, cam_obs;
+    std::vector<uint8_t> pt_var(NP, 0);
+    std::vector<float> uv(2 * NO);
+    std::vector<int> order, cnt;
+    size_t NV = 0, lds = 0;
+    cam_obs.reserve(NO);
+    for (int i = 0; i < n; ++i) {
+      WinProb& q = prob[i];
+      q = WinProb{};
+      q.cam0 = b->cam_offset[i]; q.pt0 = b->pt_offset[i]; q.obs0 = b->obs_offset[i];
+      q.nc = b->cam_offset[i + 1] - q.cam0; q.np = b->pt_offset[i + 1] - q.pt0; q.no = b->obs_offset[i + 1] - q.obs0;
+      const int32_t* oc = b->obs_cam + q.obs0;
+      const int32_t* op = b->obs_pt + q.obs0;
+      for (int k = 0; k < q.no; ++k)
+        if (oc[k] < 0 || oc[k] >= q.nc || op[k] < 0 || op[k] >= q.np)
+          throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "problem " + std::to_string(i) + ": observation " +
+                                                     std::to_string(k) + " has a local index out of range"};
+      auto cfix = [&](int c) { return b->cam_fixed && b->cam_fixed[q.cam0 + c]; };
+      auto pfix = [&](int p) { return b->pt_fixed && b->pt_fixed[q.pt0 + p]; };
+      // variable blocks that some residual touches
+      int* vc = cam_vc.data() + q.cam0;
+      for (int k = 0; k < q.no; ++k) {
+        if (!cfix(oc[k])) vc[oc[k]] = 0;
+        if (!pfix(op[k])) pt_var[q.pt0 + op[k]] = 1;
+      }
+      int nvc = 0;
+      for (int c = 0; c < q.nc; ++c) if (vc[c] == 0) vc[c] = nvc++;
+      if (nvc > BA_WINDOW_MAX_CAMS)
+        throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "problem " + std::to_string(i) + " has " + std::to_string(nvc) +
+                                                   " variable observed cameras (at most " +
+                                                   std::to_string(BA_WINDOW_MAX_CAMS) + ")"};
+      q.nvc = nvc;
+      q.vc0 = (int)NV;
+      NV += nvc;
+      lds = std::max(lds, window_lds_bytes(nvc));
+      // observations by (point, camera), stable
+      order.resize(q.no);
+      for (int k = 0; k < q.no; ++k) order[k] = k;
+      std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+        return op[x] != op[y] ? op[x] < op[y] : oc[x] < oc[y];
+      });
+      q.poff0 = q.pt0 + i;
+      int* po = pt_off.data() + q.poff0;
+      for (int k = 0; k < q.no; ++k) po[op[k] + 1]++;
+      for (int p = 0; p < q.np; ++p) po[p + 1] += po[p];
+      q.coff0 = (int)cam_off.size();
+      q.vobs0 = (int)cam_obs.size();
+      cnt.assign(nvc + 1, 0);
+      for (int k = 0; k < q.no; ++k) {
+        const int src = order[k], c = oc[src], p = op[src];
+        obs_cam[q.obs0 + k] = c;
+        uv[2 * ((size_t)q.obs0 + k)] = b->obs_uv[2 * ((size_t)q.obs0 + src)];
+        uv[2 * ((size_t)q.obs0 + k) + 1] = b->obs_uv[2 * ((size_t)q.obs0 + src) + 1];
+        if (vc[c] >= 0) {
+          cnt[vc[c] + 1]++;
+          const bool head = k == 0 || op[order[k - 1]] != p || oc[order[k - 1]] != c;
+          if (head && pt_var[q.pt0 + p]) obs_slot[q.obs0 + k] = vc[c];
+        }
+      }
+      for (int v = 0; v < nvc; ++v) cnt[v + 1] += cnt[v];
+      cam_off.insert(cam_off.end(), cnt.begin(), cnt.end());
+      cam_obs.resize(q.vobs0 + cnt[nvc]);
+      for (int k = 0; k < q.no; ++k) {
+        const int v = vc[obs_cam[q.obs0 + k]];
+        if (v >= 0) cam_obs[q.vobs0 + cnt[v]++] = k;
+      }
+    }
+    if (n == 0) {
+      ctx->win_log.clear();
+      ctx->win_log_n.clear();
+      return;
+    }
+    // ---- one buffer: inputs (uploaded) | outputs (downloaded) | scratch
+    const size_t log_cap = (size_t)std::max(o.max_num_iterations, 0) + 1;
+    if (log_cap > (size_t(1) << 40) / (sizeof(ba_iteration) * (size_t)n))
+      throw BaError{BA_ERR_OUT_OF_MEMORY, fn + "the iteration logs do not fit (max_num_iterations x n_problems)"};
+    auto al =[](size_t x) { return (x + 255) & ~size_t(255); };
+    size_t at = 0;
+    auto sec = [&](size_t bytes) { const size_t r = at; at += al(bytes); return r; };
+    const size_t o_prob = sec(sizeof(WinProb) * n), o_cams = sec(sizeof(double) * 6 * NC), o_pts = sec(sizeof(double) * 3 * NP),
+                 o_K = sec(sizeof(float) * 9 * NC), o_extr = sec(sizeof(float) * 16 * NC), o_vc = sec(sizeof(int) * NC),
+                 o_pv = sec(NP), o_poff = sec(sizeof(int) * (NP + n)), o_oc = sec(sizeof(int) * NO),
+                 o_slot = sec(sizeof(int) * NO), o_uv = sec(sizeof(float) * 2 * NO),
+                 o_coff = sec(sizeof(int) * cam_off.size()), o_cobs = sec(sizeof(int) * cam_obs.size());
+    const size_t in_b = at;
+    const size_t o_co = sec(sizeof(double) * 6 * NC), o_po = sec(sizeof(double) * 3 * NP), o_sum = sec(sizeof(double) * 8 * n),
+                 o_log = sec(sizeof(ba_iteration) * log_cap * n);
+    const size_t io_b = at;
+    const size_t w_pts = sec(sizeof(double) * 6 * NP), w_ctab = sec(sizeof(double) * 2 * kWinTbl * NC),
+                 w_vrec = sec(sizeof(double) * kWinVRec * NC), w_JR = sec(sizeof(double) * 2 * kWinJR * NO),
+                 w_Hp = sec(sizeof(double) * 18 * NP), w_sp = sec(sizeof(double) * 3 * NP),
+                 w_prec = sec(sizeof(double) * 9 * NP), w_W = sec(sizeof(double) * 18 * NO),
+                 w_hc = sec(sizeof(double) * 54 * NV);
+    const size_t total = at;
+    HIP_OK(hipSetDevice(ctx->device));
+    if (total > ctx->win_cap) {
+      if (ctx->win_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->win_buf); }
+      ctx->win_buf = nullptr;
+      ctx->win_cap = 0;
+      const hipError_t e = hipMalloc(&ctx->win_buf, total);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();   // (not sticky: the context stays usable)
+        ctx->win_buf = nullptr;
+        throw BaError{e == hipErrorOutOfMemory ? BA_ERR_OUT_OF_MEMORY : BA_ERR_DEVICE,
+                      fn + "scratch of " + std::to_string(total) + " bytes: " + hipGetErrorString(e)};
+      }
+      ctx->win_cap = total;
+    }
+    std::vector<char>& h = ctx->win_host;
+    h.resize(io_b);
+    auto put = [&](size_t off, const void* src, size_t nb) { if (nb) std::memcpy(h.data() + off, src, nb); };
+    put(o_prob, prob.data(), sizeof(WinProb) * n);
+    put(o_cams, b->cams, sizeof(double) * 6 * NC);
+    put(o_pts, b->pts, sizeof(double) * 3 * NP);
+    put(o_K, b->K, sizeof(float) * 9 * NC);
+    if (b->cam_fixed_extr) put(o_extr, b->cam_fixed_extr, sizeof(float) * 16 * NC);
+    else std::memset(h.data() + o_extr, 0, sizeof(float) * 16 * NC);
+    put(o_vc, cam_vc.data(), sizeof(int) * NC);
+    put(o_pv, pt_var.data(), NP);
+    put(o_poff, pt_off.data(), sizeof(int) * (NP + n));
+    put(o_oc, obs_cam.data(), sizeof(int) * NO);
+    put(o_slot, obs_slot.data(), sizeof(int) * NO);
+    put(o_uv, uv.data(), sizeof(float) * 2 * NO);
+    put(o_coff, cam_off.data(), sizeof(int) * cam_off.size());
+    put(o_cobs, cam_obs.data(), sizeof(int) * cam_obs.size());
+    char* d = ctx->win_buf;
+    HIP_OK(hipMemcpyAsync(d, h.data(), in_b, hipMemcpyHostToDevice, ctx->stream));
+    WinArgs A{};
+    A.prob = reinterpret_cast<const WinProb*>(d + o_prob);
+    A.NC = NC; A.NP = NP; A.NO = NO; A.NV = NV;
+    A.log_cap = (int)std::min<size_t>(log_cap, 0x7fffffff);
+    A.huber_a = b->huber_a;
+    auto dd = [&](size_t off) { return reinterpret_cast<double*>(d + off); };
+    auto di = [&](size_t off) { return reinterpret_cast<const int*>(d + off); };
+    A.cams_in = dd(o_cams); A.pts_in = dd(o_pts);
+    A.K = reinterpret_cast<const float*>(d + o_K); A.extr = reinterpret_cast<const float*>(d + o_extr);
+    A.cam_vc = di(o_vc); A.pt_var = reinterpret_cast<const uint8_t*>(d + o_pv);
+    A.pt_off = di(o_poff); A.obs_cam = di(o_oc); A.obs_slot = di(o_slot);
+    A.uv = reinterpret_cast<const float2*>(d + o_uv);
+    A.cam_off = di(o_coff); A.cam_obs = di(o_cobs);
+    A.pts = dd(w_pts); A.ctab = dd(w_ctab); A.vrec = dd(w_vrec); A.JR = dd(w_JR); A.Hp = dd(w_Hp);
+    A.scale_p = dd(w_sp); A.prec = dd(w_prec); A.Wb = dd(w_W); A.hc = dd(w_hc);
+    A.cams_out = dd(o_co); A.pts_out = dd(o_po); A.summ = dd(o_sum); A.log = d + o_log;
+    PoseOpts po{o.max_num_iterations, o.max_num_consecutive_invalid_steps, o.jacobi_scaling,
+                o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance, o.initial_trust_region_radius,
+                o.max_trust_region_radius, o.min_trust_region_radius, o.min_relative_decrease, o.min_lm_diagonal,
+                o.max_lm_diagonal};
+    const double t_prep = now_s() - t0;
+    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
+    HIP_OK((hipError_t)launch_window_batch(n, A, po, lds, ctx->stream));
+    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
+    HIP_OK(hipMemcpyAsync(h.data() + in_b, d + in_b, io_b - in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    float kernel_ms = 0.0f;
+    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
+    if (NC) std::memcpy(cams_out, h.data() + o_co, sizeof(double) * 6 * NC);
+    if (NP) std::memcpy(pts_out, h.data() + o_po, sizeof(double) * 3 * NP);
+    const double* sm = reinterpret_cast<const double*>(h.data() + o_sum);
+    ctx->win_log_cap = A.log_cap;
+    ctx->win_log_n.resize(n);
+    const ba_iteration* lg = reinterpret_cast<const ba_iteration*>(h.data() + o_log);
+    ctx->win_log.assign(lg, lg + log_cap * n);
+    const double wall = now_s() - t0;
+    ctx->win_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * wall};
+    for (int i = 0; i < n; ++i) {
+      ctx->win_log_n[i] = (int)sm[8 * i + 6];
+      if (!summaries) continue;
+      ba_summary S{};
+      S.initial_cost = sm[8 * i];
+      S.final_cost = sm[8 * i + 1];
+      S.num_iterations = (int)sm[8 * i + 2];
+      S.num_successful_steps = (int)sm[8 * i + 3];
+      S.num_unsuccessful_steps = (int)sm[8 * i + 4];
+      S.termination_type = (int)sm[8 * i + 5];
+      S.total_time_s = S.linearize_time_s = S.solve_time_s = wall;
+      summaries[i] = S;
+    }
+  });
+}
+
+int ba_get_window_iteration_log(ba_ctx* ctx, int problem, ba_iteration* out, int n) {
+  if (!ctx || problem < 0 || problem >= (int)ctx->win_log_n.size()) return -BA_ERR_INVALID_ARGUMENT;
+  const int avail = ctx->win_log_n[problem];
+  const int k = std::min(n, avail);
+  if (out && k > 0)
+    std::memcpy(out, ctx->win_log.data() + (size_t)problem * ctx->win_log_cap, sizeof(ba_iteration) * k);
+  return avail;
+}
+
+int ba_window_times(ba_ctx* ctx, double* ms, int n) {
+  if (!ctx) return -BA_ERR_INVALID_ARGUMENT;
+  const int m = (int)ctx->win_ms.size();
+  for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = ctx->win_ms[i];
+  return m;
 }
 
 int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double* Hcc, double* gc, double* S,

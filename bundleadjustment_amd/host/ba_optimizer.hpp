@@ -47,6 +47,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -66,6 +67,13 @@ class HipBackend {
   explicit HipBackend(int device = 0) {
     const int st = ba_create(&ctx_, device);
     if (st != BA_OK) throw std::runtime_error("ba_create failed (status " + std::to_string(st) + ")");
+    // BA_WINDOW_SOLVER (read once; opt-in): 0 / unset: the general path;
+    // 1: problems that fit go through ba_solve_window_batch (the whole LM
+    // loop in one launch), the others the general way; 2: as 1, but a problem
+    // that does not fit is BA_ERR_INVALID_ARGUMENT (proves which path ran)
+    const char* w = std::getenv("BA_WINDOW_SOLVER");
+    window_mode_ = w ? std::atoi(w) : 0;
+    if (window_mode_ < 0 || window_mode_ > 2) window_mode_ = 0;
   }
   ~HipBackend() { ba_destroy(ctx_); }
   HipBackend(const HipBackend&) = delete;
@@ -73,6 +81,7 @@ class HipBackend {
 
   int solve(const ba_problem& p, const ba_options& o, double* cams, double* pts, ba_summary* s) {
     if (pose_only(p)) return solve_pose(p, o, cams, pts, s);
+    if (window_mode_ == 2 || (window_mode_ == 1 && fits_window(p))) return solve_window(p, o, cams, pts, s);
     int st = ba_set_problem(ctx_, &p);
     if (st == BA_OK) st = ba_solve(ctx_, &o, s);
     if (st == BA_OK) st = ba_get_params(ctx_, cams, pts);
@@ -106,10 +115,37 @@ class HipBackend {
     if (st == BA_OK && pts && p.n_pts > 0) std::copy(p.pts, p.pts + 3 * static_cast<size_t>(p.n_pts), pts);
     return st;
   }
+  // A local-BA-sized problem: at most BA_WINDOW_MAX_CAMS variable cameras
+  // with observations (constant observers are not limited).
+  static bool fits_window(const ba_problem& p) {
+    std::vector<uint8_t> seen(static_cast<size_t>(std::max<int32_t>(p.n_cams, 0)), 0);
+    int nvc = 0;
+    for (int32_t k = 0; k < p.n_obs; ++k) {
+      const int32_t c = p.obs_cam[k];
+      if (c < 0 || c >= p.n_cams) return false;   // (the general path reports it)
+      if ((p.cam_fixed && p.cam_fixed[c]) || seen[c]) continue;
+      seen[c] = 1;
+      if (++nvc > BA_WINDOW_MAX_CAMS) return false;
+    }
+    return true;
+  }
+  int solve_window(const ba_problem& p, const ba_options& o, double* cams, double* pts, ba_summary* s) {
+    const int32_t co[2] = {0, p.n_cams}, po[2] = {0, p.n_pts}, oo[2] = {0, p.n_obs};
+    ba_window_batch b{};
+    b.n_problems = 1;
+    b.cam_offset = co; b.pt_offset = po; b.obs_offset = oo;
+    b.cams = p.cams; b.cam_fixed = p.cam_fixed; b.cam_fixed_extr = p.cam_fixed_extr; b.K = p.K;
+    b.pts = p.pts; b.pt_fixed = p.pt_fixed;
+    b.obs_cam = p.obs_cam; b.obs_pt = p.obs_pt; b.obs_uv = p.obs_uv;
+    b.huber_a = p.huber_a;
+    return ba_solve_window_batch(ctx_, &b, &o, cams, pts, s);
+  }
+  int window_mode() const { return window_mode_; }
   std::string last_error() const { return ba_last_error(ctx_); }
 
  private:
   ba_ctx* ctx_ = nullptr;
+  int window_mode_ = 0;
 };
 
 // Host SoA of one ba_problem (the gather of prepareConstraints).

@@ -335,6 +335,67 @@ def make_config(name: str, scale: float = 1.0, **overrides) -> Problem:
     return make_synthetic(seed=seed, name=name, **cfg)
 
 
+@dataclass
+class WindowBatch:
+    """Independent small problems concatenated in the layout of the C-ABI's
+    ba_window_batch: problem i owns cameras [cam_offset[i], cam_offset[i+1]),
+    points [pt_offset[i], pt_offset[i+1]) and observations [obs_offset[i],
+    obs_offset[i+1]); obs_cam / obs_pt stay local to their problem."""
+    cam_offset: np.ndarray      # (n + 1,) int32
+    pt_offset: np.ndarray       # (n + 1,) int32
+    obs_offset: np.ndarray      # (n + 1,) int32
+    cams: np.ndarray            # (C, 6) float64
+    cam_fixed: np.ndarray       # (C,) uint8
+    cam_fixed_extr: np.ndarray  # (C, 16) float32
+    K: np.ndarray               # (C, 9) float32
+    pts: np.ndarray             # (P, 3) float64
+    pt_fixed: np.ndarray        # (P,) uint8
+    obs_cam: np.ndarray         # (N,) int32
+    obs_pt: np.ndarray          # (N,) int32
+    obs_uv: np.ndarray          # (N, 2) float32
+    huber_a: float = HUBER_A
+
+    @property
+    def n_problems(self) -> int:
+        return int(self.cam_offset.shape[0]) - 1
+
+
+def pack_window_batch(problems: list[Problem]) -> WindowBatch:
+    """Concatenate problems for Solver.solve_window_batch (pure numpy).  A
+    missing cam_fixed / pt_fixed becomes zeros, a missing cam_fixed_extr zeros
+    (never read for variable cameras).  huber_a is one value per batch: the
+    problems must agree on it."""
+    ps = [p.normalized() for p in problems]
+    huber = {float(p.huber_a) for p in ps}
+    if len(huber) > 1:
+        raise ValueError(f"pack_window_batch: the problems disagree on huber_a: {sorted(huber)}")
+
+    def off(counts):
+        o = np.zeros(len(ps) + 1, np.int64)
+        np.cumsum(counts, out=o[1:])
+        if o[-1] > np.iinfo(np.int32).max:
+            raise ValueError("pack_window_batch: the batch does not fit 32-bit offsets")
+        return o.astype(np.int32)
+
+    def cat(arrs, dt, tail):
+        arrs = [np.asarray(a, dt).reshape((-1,) + tail) for a in arrs]
+        return np.ascontiguousarray(np.concatenate(arrs, axis=0) if arrs else np.zeros((0,) + tail, dt), dtype=dt)
+
+    return WindowBatch(
+        cam_offset=off([p.n_cams for p in ps]), pt_offset=off([p.n_pts for p in ps]),
+        obs_offset=off([p.n_obs for p in ps]),
+        cams=cat([p.cams for p in ps], np.float64, (6,)),
+        cam_fixed=cat([np.zeros(p.n_cams, np.uint8) if p.cam_fixed is None else p.cam_fixed for p in ps], np.uint8, ()),
+        cam_fixed_extr=cat([np.zeros((p.n_cams, 16), np.float32) if p.cam_fixed_extr is None else p.cam_fixed_extr
+                            for p in ps], np.float32, (16,)),
+        K=cat([p.K for p in ps], np.float32, (9,)),
+        pts=cat([p.pts for p in ps], np.float64, (3,)),
+        pt_fixed=cat([np.zeros(p.n_pts, np.uint8) if p.pt_fixed is None else p.pt_fixed for p in ps], np.uint8, ()),
+        obs_cam=cat([p.obs_cam for p in ps], np.int32, ()), obs_pt=cat([p.obs_pt for p in ps], np.int32, ()),
+        obs_uv=cat([p.obs_uv for p in ps], np.float32, (2,)),
+        huber_a=huber.pop() if huber else HUBER_A)
+
+
 def shard_points(problem: Problem, nranks: int, rank: int, bounds: list[int] | None = None) -> Problem:
     """Point-sharded slice for multi-GPU: contiguous point
     ranges balanced by observation count (or the given `bounds`, nranks + 1

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as N
-from .problem import HUBER_A, Problem
+from .problem import HUBER_A, Problem, WindowBatch, pack_window_batch
 
 
 def _ptr(a):
@@ -290,6 +290,52 @@ class Solver:
                        s.num_unsuccessful_steps, N.TERMINATION_NAMES.get(s.termination_type, str(s.termination_type)),
                        s.total_time_s, s.linearize_time_s, s.solve_time_s) for s in list(sums)[:n]]
         return out, res
+
+    def solve_window_batch(self, problems, options: Options | None = None
+                           ) -> tuple[list[tuple[np.ndarray, np.ndarray]], list[Summary]]:
+        """Many independent small problems (variable cameras and points, at
+        most BA_WINDOW_MAX_CAMS variable observed cameras each) with solve()'s
+        DENSE_SCHUR semantics, the whole LM loop of each problem in one kernel
+        launch (ba_solve_window_batch).  `problems`: a list of Problem (packed
+        with pack_window_batch) or a WindowBatch.  Returns ([(cams, pts) per
+        problem], summaries); window_iteration_log(i) has problem i's log."""
+        b = problems if isinstance(problems, WindowBatch) else pack_window_batch(list(problems))
+        n = b.n_problems
+        w = N.ba_window_batch(
+            n_problems=n, reserved=0, cam_offset=_ptr(b.cam_offset), pt_offset=_ptr(b.pt_offset),
+            obs_offset=_ptr(b.obs_offset), cams=_ptr(b.cams), cam_fixed=_ptr(b.cam_fixed),
+            cam_fixed_extr=_ptr(b.cam_fixed_extr), K=_ptr(b.K), pts=_ptr(b.pts), pt_fixed=_ptr(b.pt_fixed),
+            obs_cam=_ptr(b.obs_cam), obs_pt=_ptr(b.obs_pt), obs_uv=_ptr(b.obs_uv), huber_a=float(b.huber_a))
+        o = (options or Options()).to_c()
+        cams = np.empty_like(b.cams)
+        pts = np.empty_like(b.pts)
+        sums = (N.ba_summary * max(n, 1))()
+        self._check(self.lib.ba_solve_window_batch(self.h, C.byref(w), C.byref(o), _ptr(cams), _ptr(pts), sums),
+                    "ba_solve_window_batch")
+        co, po = b.cam_offset, b.pt_offset
+        out = [(cams[co[i]:co[i + 1]].copy(), pts[po[i]:po[i + 1]].copy()) for i in range(n)]
+        res = [Summary(s.initial_cost, s.final_cost, s.num_iterations, s.num_successful_steps,
+                       s.num_unsuccessful_steps, N.TERMINATION_NAMES.get(s.termination_type, str(s.termination_type)),
+                       s.total_time_s, s.linearize_time_s, s.solve_time_s) for s in list(sums)[:n]]
+        return out, res
+
+    def window_iteration_log(self, i: int) -> list[dict]:
+        """Iteration log of problem i of the last solve_window_batch."""
+        n = self.lib.ba_get_window_iteration_log(self.h, int(i), None, 0)
+        if n < 0:
+            raise N.BAError(-n, f"ba_get_window_iteration_log: no problem {i} in the last batch")
+        arr = (N.ba_iteration * max(n, 1))()
+        self.lib.ba_get_window_iteration_log(self.h, int(i), arr, n)
+        return [{f: getattr(arr[k], f) for f in ITER_FIELDS} for k in range(n)]
+
+    def window_times(self) -> np.ndarray:
+        """Times (ms) of the last solve_window_batch: host preparation (wall),
+        the kernel (device), the whole call (wall)."""
+        n = self.lib.ba_window_times(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            self.lib.ba_window_times(self.h, _ptr(out), n)
+        return out
 
     def synchronize(self):
         self._check(self.lib.ba_synchronize(self.h), "ba_synchronize")

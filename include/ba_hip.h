@@ -274,6 +274,71 @@ typedef struct {
 int ba_solve_pose_batch(ba_ctx* ctx, const ba_pose_batch* batch, const ba_options* opt, double* cams_out,
                         ba_summary* summaries);
 
+/* Batched small-window bundle adjustment: many independent problems, each
+ * with variable cameras AND variable points, solved with ba_solve's
+ * DENSE_SCHUR semantics; the whole Levenberg-Marquardt loop of a problem runs
+ * inside one kernel launch (one workgroup per problem).  Replaces, per
+ * window, the ceres::Problem + ceres::Solve of LocalBAOptimizerAngles
+ * (Optimizer.cpp:500-698: the current keyframe and its covisible frames
+ * variable, the other observers as PointOnlyReprojectionError) and of the
+ * small global BAs.
+ *
+ * Problem i owns cameras [cam_offset[i], cam_offset[i+1]), points
+ * [pt_offset[i], pt_offset[i+1]) and observations [obs_offset[i],
+ * obs_offset[i+1]) of the concatenated arrays (those of ba_problem);
+ * obs_cam / obs_pt index the problem's own cameras and points.  It is solved
+ * as ba_set_problem + ba_solve (BA_DENSE_SCHUR, BA_FP64) + ba_get_params
+ * would solve the equivalent ba_problem: the four residual kinds, Huber loss,
+ * Jacobi scaling from iteration 0, clamped LM diagonal, the same termination
+ * rules, invalid-step handling and radius updates.  Duplicate observations
+ * are allowed; parameter blocks without observations are returned untouched.
+ * At most BA_WINDOW_MAX_CAMS variable cameras with observations per problem
+ * (constant cameras are not limited).
+ *
+ * cams_out[6*n_cams] / pts_out[3*n_pts] receive all parameter blocks (may
+ * alias the inputs); summaries[i] (may be NULL) the per-problem summary (time
+ * fields: the batch's wall time).  Non-convergence or a numeric failure of
+ * one problem is reported in its summary only (a non-finite cost: BA_FAILURE,
+ * parameters as last accepted) and does not affect its neighbours.  A
+ * problem's result is bitwise reproducible and does not depend on its place
+ * in the batch or on the other problems.
+ *
+ * Errors (the context stays usable; its current problem is not touched, a
+ * ba_solve before and after is bit for bit what it would have been; no
+ * collective is used):
+ *   BA_ERR_INVALID_ARGUMENT  an offset array that decreases, a local index
+ *                            out of range, more than BA_WINDOW_MAX_CAMS
+ *                            variable observed cameras (the message names the
+ *                            problem); linear_solver != BA_DENSE_SCHUR;
+ *                            precision != BA_FP64,
+ *   BA_ERR_OUT_OF_MEMORY     the scratch cannot be allocated. */
+#define BA_WINDOW_MAX_CAMS 16   /* variable, observed cameras per problem (reference: <= 11) */
+
+typedef struct {
+  int32_t n_problems, reserved;
+  const int32_t* cam_offset;   /* [n_problems+1], [0] = 0, non-decreasing */
+  const int32_t* pt_offset;    /* [n_problems+1] */
+  const int32_t* obs_offset;   /* [n_problems+1] */
+  /* the arrays of ba_problem, concatenated over the problems */
+  const double*  cams;  const uint8_t* cam_fixed;  const float* cam_fixed_extr;  const float* K;
+  const double*  pts;   const uint8_t* pt_fixed;
+  const int32_t* obs_cam;      /* index LOCAL to the problem: 0 .. n_cams(i)-1 */
+  const int32_t* obs_pt;       /* local: 0 .. n_pts(i)-1 */
+  const float*   obs_uv;
+  double huber_a;              /* per batch, as in ba_pose_batch */
+} ba_window_batch;
+
+int ba_solve_window_batch(ba_ctx* ctx, const ba_window_batch* batch, const ba_options* opt, double* cams_out,
+                          double* pts_out, ba_summary* summaries /* may be NULL */);
+/* Iteration log of problem `problem` of the last ba_solve_window_batch; same
+ * contract as ba_get_iteration_log (iteration_time_s is 0). */
+int ba_get_window_iteration_log(ba_ctx* ctx, int problem, ba_iteration* out, int n);
+/* Times (ms) of the last successful ba_solve_window_batch: [0] host
+ * preparation (structure, staging, upload enqueue; wall), [1] the kernel
+ * (device, HIP events), [2] the whole call (wall).  Copies min(n, 3) values,
+ * returns 3 (0 before the first call).  Diagnostic. */
+int ba_window_times(ba_ctx* ctx, double* ms, int n);
+
 /* Test / inspection entry point: the state inside ceres::Solve's
  * SchurComplementSolver (Optimizer.cpp:242, DENSE_SCHUR) for one step.
  * Linearises at the current parameters with iteration-0 Jacobi scaling, then
