@@ -104,8 +104,17 @@ __device__ __forceinline__ void split_critical(double* __restrict__ A, double* _
   if (threadIdx.x == 0 && cw.bad) scal[SL_CHOL_BAD] += 1.0;
 }
 
+// glast (the solver's rank-64 form): the sums are grouped as the task table
+// groups them, so the factor is bitwise the scheduled forms'.  A tile's
+// products of the panels of one range [pa, pb) of the table are accumulated
+// in the MFMA accumulators, carried from step to step through U (continuing
+// an accumulation from memory rounds as continuing it in registers), and the
+// range's last panel writes A - acc; glast[(I * T + J) * T + p] marks the
+// panels that end a range of tile (I, J).  Null: every panel on its own.
 __global__ __launch_bounds__(256) void k_chol_step_split(double* __restrict__ A, double* __restrict__ L, int ld, int n,
-                                                   int k, double* __restrict__ Vbuf, double* __restrict__ scal) {
+                                                   int k, double* __restrict__ Vbuf, double* __restrict__ scal,
+                                                   const unsigned char* __restrict__ glast,
+                                                   double* __restrict__ U) {
   int I, J;
   split_tile_of(blockIdx.x, (n - (k + 1) * CB + CB - 1) / CB, I, J);
   // two tiles + a narrow inverse scratch (78 KB: two workgroups per CU, so
@@ -145,11 +154,14 @@ __global__ __launch_bounds__(256) void k_chol_step_split(double* __restrict__ A,
         acc_pos(a, b, g, &rr, &cc);
         av[a][b][g] = A[(size_t)min(r0 + rr, nrows - 1) * ld + min(c0 + cc, n - 1)];
       }
-  if (I != J) tile_put(S1, tJ);
-  tile_put(S0, tI);
-  __syncthreads();
+  bool first = true, last = true;   // panel k starts / ends a range of this tile
+  if (glast) {
+    const int T = (n + CB - 1) / CB;
+    const unsigned char* g = glast + ((size_t)(k + 1 + I) * T + (k + 1 + J)) * T;
+    last = g[k] != 0;
+    first = k == 0 || g[k - 1] != 0;
+  }
   d4 acc[2][2];
-  mfma_xyT_64(S0, I != J ? S1 : S0, acc);
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -159,7 +171,25 @@ __global__ __launch_bounds__(256) void k_chol_step_split(double* __restrict__ A,
         int rr, cc;
         acc_pos(a, b, g, &rr, &cc);
         const int ri = r0 + rr, cj = c0 + cc;
-        if (ri < nrows && cj < n && cj <= ri) A[(size_t)ri * ld + cj] = av[a][b][g] - acc[a][b][g];
+        acc[a][b][g] = (!first && ri < nrows && cj < n && cj <= ri) ? U[(size_t)ri * ld + cj] : 0.0;
+      }
+  if (I != J) tile_put(S1, tJ);
+  tile_put(S0, tI);
+  __syncthreads();
+  mfma_xyT_64_add(S0, I != J ? S1 : S0, acc);
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        int rr, cc;
+        acc_pos(a, b, g, &rr, &cc);
+        const int ri = r0 + rr, cj = c0 + cc;
+        if (ri < nrows && cj < n && cj <= ri) {
+          if (last) A[(size_t)ri * ld + cj] = av[a][b][g] - acc[a][b][g];
+          else U[(size_t)ri * ld + cj] = acc[a][b][g];
+        }
       }
 }
 
@@ -396,8 +426,10 @@ __device__ __forceinline__ bool upd_tile(double* __restrict__ A, double* __restr
 //    front-loaded trailing work becomes a steady background the chain's
 //    serial steps hide.
 // At most one task per tile per launch; bitwise deterministic for a given
-// order (not bitwise the rank-64 form: the sums are grouped differently —
-// parity is against the oracle, as before).
+// order and rank.  The rank-64 form takes a panel per launch but groups its
+// sums by the default table's ranges (chol_rank64_groups), so it is bitwise
+// the scheduled forms too; a table of another rank (BA_CHOL_RANK != 4, 0)
+// groups differently and is not.
 struct CholSplitPlan {
   std::vector<int4> tasks;   // {I, J, pa, pb}, step-major
   std::vector<int> off;      // step k's tasks: [off[k], off[k + 1])
@@ -630,6 +662,18 @@ static double chol_split_budget() {
   return v > 0 ? v : 1.0;
 }
 
+// The rank-64 form's summation groups: the ranges of the default task table
+// (rank 4), last[(I * T + J) * T + p] = 1 where panel p ends a range of tile
+// (I, J) (k_chol_step_split).
+void chol_rank64_groups(int n, std::vector<unsigned char>& last) {
+  const int T = (n + CB - 1) / CB, TR = (n + 1 + CB - 1) / CB;
+  CholSplitPlan P;
+  chol_split_plan(T, TR, 4, chol_split_budget(), P);
+  last.assign((size_t)TR * T * T, 0);
+  for (const int4& t : P.tasks)
+    if (t.w > t.z) last[((size_t)(t.x & 0xfffff) * T + t.y) * T + t.w - 1] = 1;
+}
+
 // The task table of an order-n system (device copy + host step offsets).
 void chol_split_tasks(int n, std::vector<int4>& tasks, std::vector<int>& off) {
   const int T = (n + CB - 1) / CB, TR = (n + 1 + CB - 1) / CB;
@@ -711,7 +755,8 @@ int chol_split_fused() {
 // (the fused form): panel k was formed by step k - 1's column tasks (k = 0:
 // k_chol_panel here), else k_chol_panel forms it now.
 void launch_chol_split_step(double* A, double* L, int ld, int n, int k, int tc, int tr, double* Vbuf, double* scal,
-                            const int4* tasks, const int* off, unsigned* vflag, unsigned epoch, hipStream_t s) {
+                            const int4* tasks, const int* off, unsigned* vflag, unsigned epoch, hipStream_t s,
+                            const unsigned char* glast, double* U) {
   if (!vflag || !tasks || k == 0) hipLaunchKernelGGL(k_chol_panel, dim3(tr), dim3(256), 0, s, A, L, ld, n, k, Vbuf);
   if (tasks) {
     const char* e = getenv("BA_CHOL_SPIN_MAX");   // (diagnostics: a small bound exercises the fallback)
@@ -721,7 +766,7 @@ void launch_chol_split_step(double* A, double* L, int ld, int n, int k, int tc, 
     return;
   }
   const int ntiles = tc * (tc + 1) / 2 + (tr > tc ? tc : 0);   // lower tiles (+ a rhs-only tile row)
-  hipLaunchKernelGGL(k_chol_step_split, dim3(ntiles), dim3(256), 0, s, A, L, ld, n, k, Vbuf, scal);
+  hipLaunchKernelGGL(k_chol_step_split, dim3(ntiles), dim3(256), 0, s, A, L, ld, n, k, Vbuf, scal, U ? glast : nullptr, U);
 }
 
 }  // namespace bahip

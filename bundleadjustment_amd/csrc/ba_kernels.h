@@ -98,12 +98,13 @@ struct DevWork {
   bool wcompact;                     // W as 128-B compact records (J-free fp64 DENSE_SCHUR; ba_kernels.hip)
   double* S;                         // [(n+1) x ld] reduced system, row n = rhs (working matrix)
   double* Lf;                        // [(n+1) x ld] Cholesky factor, row n = L^-1 rhs
-  double* Ubuf;                      // [(n+1) x ld] the per-step Cholesky's update accumulator (< kCholSplitBlocks block columns)
+  double* Ubuf;                      // [(n+1) x ld] the per-step Cholesky's update accumulator (< kCholSplitBlocks block columns, and the rank-64 form)
   double* Spk;                       // [n(n+1)/2 + n] packed lower triangle + rhs of S (multi-rank exchange)
   double* y;                         // [n] reduced solution
   double* Vbuf;                      // [ceil(n/64)][64][64] inverses of the diagonal Cholesky blocks
   const int4* ctask;                 // split Cholesky task table {I, J, pa, pb} (>= kCholSplitBlocks block columns; null: rank-64 form)
   const int* ctask_off;              // host: step k's tasks [ctask_off[k], ctask_off[k+1])
+  const unsigned char* r64_last;     // rank-64 form: [TR][T][T] panel p ends a range of the task table for tile (I, J)
   bool chol_fuse;                    // split form: column tasks form the next panel in-launch (flags: cflags[0, T))
   bool chol_flow;                    // split form: the whole factorisation as one dataflow launch (k_chol_flow)
   const int4* ftask; int nftask;     // ... its task list
@@ -253,6 +254,7 @@ bool obs_w_pc_ok(const DevProblem& P, const DevWork& W);   // k_obs_w_rc has the
 bool chol_persist_fits(int device, int n);   // every workgroup of k_chol_persist resident at once
 void chol_split_tasks(int n, std::vector<int4>& tasks, std::vector<int>& off);   // the split form's task table
 int chol_split_rank();
+void chol_rank64_groups(int n, std::vector<unsigned char>& last);   // the rank-64 form's summation groups (the task table's ranges)
 int chol_split_fused();                      // BA_CHOL_FUSE (default 1)
 int chol_split_flow();                       // BA_CHOL_FLOW (default 1)
 void chol_flow_tasks(const std::vector<int4>& tasks, const std::vector<int>& off, std::vector<int4>& flow);                       // panels per split-Cholesky task (BA_CHOL_RANK, default 4; 0: rank-64 form)

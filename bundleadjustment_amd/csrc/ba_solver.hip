@@ -637,8 +637,15 @@ void ensure_dense(ba_ctx* ctx) {
   DevWork& W = ctx->W;
   W.S = ctx->dalloc<double>((size_t)(ctx->n + 1) * std::max(ctx->ld, 1));
   W.Lf = ctx->dalloc<double>((size_t)(ctx->n + 1) * std::max(ctx->ld, 1));
-  W.Ubuf = (ctx->n + 63) / 64 < bahip::chol_split_blocks()
+  const bool rank64 = (ctx->n + 63) / 64 >= bahip::chol_split_blocks() && bahip::chol_split_rank() == 0;
+  W.Ubuf = (ctx->n + 63) / 64 < bahip::chol_split_blocks() || rank64
                ? ctx->dalloc<double>((size_t)(ctx->n + 1) * std::max(ctx->ld, 1)) : nullptr;
+  W.r64_last = nullptr;
+  if (rank64) {
+    std::vector<unsigned char> last;
+    bahip::chol_rank64_groups(ctx->n, last);
+    W.r64_last = ctx->upload(last);
+  }
   W.Vbuf = ctx->dalloc<double>((size_t)((ctx->n + 63) / 64 + 1) * 64 * 64);
   W.ctask = nullptr;
   W.ctask_off = nullptr;
@@ -1461,6 +1468,99 @@ void covariance(ba_ctx* ctx, const ba_covariance_request* req) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// ba_debug_factor: the DENSE_SCHUR factorisation + back substitution of a
+// step (launch_cholesky_solve2) on a caller-supplied system of the problem's
+// order.  The overlapped form forms S inside its own launch and cannot take an
+// injected matrix: it is not reachable from here (its bitwise test against the
+// separate passes covers it).
+// ---------------------------------------------------------------------------
+void debug_factor(ba_ctx* ctx, const double* S_in, const double* rhs_in, double* L, double* V, double* y, int* ok) {
+  if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, "ba_debug_factor before ba_set_problem"};
+  if (ctx->has_comm())
+    throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_debug_factor: not available on a context with a communicator"};
+  if (ctx->n == 0) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_debug_factor: the problem has no variable observed camera"};
+  if (!S_in || !rhs_in) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_debug_factor: S_in / rhs_in is NULL"};
+  HIP_OK(hipSetDevice(ctx->device));
+  ensure_dense(ctx);   // (refuses a system too large for DENSE_SCHUR)
+  const hipStream_t s = ctx->stream;
+  DevWork& W = ctx->W;
+  const size_t n = (size_t)ctx->n, ld = (size_t)ctx->ld, T = (n + 63) / 64;
+  // the (n+1) x ld trapezoid: lower triangle of S_in, row n = rhs; what the
+  // kernels do not read stays zero (the solver's state)
+  std::vector<double> m((n + 1) * ld, 0.0);
+  for (size_t i = 0; i < n; ++i) std::copy(S_in + i * n, S_in + i * n + i + 1, m.begin() + i * ld);
+  std::copy(rhs_in, rhs_in + n, m.begin() + n * ld);
+  // a solve's steps overwrite y before they read it; other consumers of the
+  // context (ITERATIVE_SCHUR) own it between calls: put it back afterwards
+  std::vector<double> y_keep(n);
+  HIP_OK(hipMemcpyAsync(y_keep.data(), W.y, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  double flags[2] = {0.0, 0.0};   // SL_CHOL_BAD, SL_CHOL_SPIN
+  for (int attempt = 0;; ++attempt) {
+    HIP_OK(hipMemcpyAsync(W.S, m.data(), sizeof(double) * m.size(), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemsetAsync(W.scal + SL_CHOL_BAD, 0, sizeof(double), s));
+    HIP_OK(hipMemsetAsync(W.scal + SL_CHOL_SPIN, 0, sizeof(double), s));
+    launch_cholesky_solve2(ctx->P, W, ++ctx->chol_epoch, s);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(&flags[0], W.scal + SL_CHOL_BAD, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(&flags[1], W.scal + SL_CHOL_SPIN, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (flags[1] == 0.0) break;
+    // a hand-off of the factorisation never came: as in ba_covariance, once
+    // more with the per-step launches (kept for this context)
+    if (attempt > 0 || (!W.chol_persist && !W.chol_fuse && !W.chol_flow)) {
+      HIP_OK(hipMemsetAsync(W.S, 0, sizeof(double) * m.size(), s));
+      HIP_OK(hipMemsetAsync(W.scal + SL_CHOL_BAD, 0, sizeof(double), s));
+      HIP_OK(hipMemsetAsync(W.scal + SL_CHOL_SPIN, 0, sizeof(double), s));
+      HIP_OK(hipMemcpyAsync(W.y, y_keep.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
+      HIP_OK(hipStreamSynchronize(s));
+      throw BaError{BA_ERR_DEVICE, "dense Cholesky: a hand-off spin bound was hit"};
+    }
+    W.chol_persist = W.chol_flow = W.chol_fuse = false;
+  }
+  if (L) {
+    HIP_OK(hipMemcpyAsync(L, W.Lf, sizeof(double) * (n + 1) * n, hipMemcpyDeviceToHost, s));   // (ld == n)
+    HIP_OK(hipStreamSynchronize(s));
+    // rows < n: the kernels store the tiles left of the diagonal 64-block
+    // only; the rest of the buffer is stale
+    for (size_t i = 0; i < n; ++i) std::fill(L + i * n + (i / 64) * 64, L + (i + 1) * n, 0.0);
+    if (n % 64 == 0) {
+      // the rhs row is a tile row of its own: no step factors it into z's
+      // last block, k_back_flow forms z_K = V_K A_{n,K}^T in LDS from the
+      // updated rhs row and stores nothing; the same product here (its
+      // summation order: four strided partial sums, then their pairwise sum)
+      const size_t K = T - 1;
+      std::vector<double> a(64), v(64 * 64);
+      HIP_OK(hipMemcpyAsync(a.data(), W.S + n * ld + K * 64, sizeof(double) * 64, hipMemcpyDeviceToHost, s));
+      HIP_OK(hipMemcpyAsync(v.data(), W.Vbuf + K * 64 * 64, sizeof(double) * 64 * 64, hipMemcpyDeviceToHost, s));
+      HIP_OK(hipStreamSynchronize(s));
+      for (size_t j = 0; j < 64; ++j) {
+        double part[4];
+        for (size_t h = 0; h < 4; ++h) {
+          double t = 0.0;
+          for (size_t q = 0; q < 16; ++q) {
+            const size_t i = h + 4 * q;
+            t = std::fma(i <= j ? v[j * 64 + i] : 0.0, a[i], t);
+          }
+          part[h] = t;
+        }
+        L[n * n + K * 64 + j] = (part[0] + part[1]) + (part[2] + part[3]);
+      }
+    }
+  }
+  if (V) HIP_OK(hipMemcpyAsync(V, W.Vbuf, sizeof(double) * T * 64 * 64, hipMemcpyDeviceToHost, s));
+  if (y) HIP_OK(hipMemcpyAsync(y, W.y, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  // S held the updated trailing matrix: back to zeros, its state before the
+  // first step (ensure_dense; the steps rely on its never-written blocks being
+  // zero); the failure slots as a step's first kernels leave them
+  HIP_OK(hipMemsetAsync(W.S, 0, sizeof(double) * m.size(), s));
+  HIP_OK(hipMemsetAsync(W.scal + SL_CHOL_BAD, 0, sizeof(double), s));
+  HIP_OK(hipMemsetAsync(W.scal + SL_CHOL_SPIN, 0, sizeof(double), s));
+  HIP_OK(hipMemcpyAsync(W.y, y_keep.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (ok) *ok = flags[0] == 0.0 ? 1 : 0;
+}
+
 }  // namespace
 
 // ============================================================================
@@ -2093,6 +2193,11 @@ int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double*
     }
     if (n_out) *n_out = n;
   });
+}
+
+int ba_debug_factor(ba_ctx* ctx, const double* S_in, const double* rhs_in, double* L, double* V, double* y, int* ok) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { debug_factor(ctx, S_in, rhs_in, L, V, y, ok); });
 }
 
 int ba_covariance(ba_ctx* ctx, const ba_covariance_request* req) {

@@ -223,6 +223,38 @@ class Solver:
                                              C.byref(n)), "ba_debug_blocks")
         return {"Hpp": Hpp, "gp": gp, "Hcc": Hcc, "gc": gc, "S": S, "rhs": rhs, "n": n.value}
 
+    def reduced_order(self) -> int:
+        """Order n of the current problem's reduced camera system: 6 x the
+        variable cameras that have an observation."""
+        p = self.problem
+        used = np.zeros(p.n_cams, bool)
+        used[p.obs_cam] = True
+        if p.cam_fixed is not None:
+            used &= np.asarray(p.cam_fixed) == 0
+        return 6 * int(used.sum())
+
+    def debug_factor(self, S, rhs) -> dict:
+        """The DENSE_SCHUR factorisation + back substitution of a solve's step
+        on a caller-supplied system of the current problem's order
+        (ba_debug_factor; the form is the one the order and the BA_CHOL_*
+        knobs select).  S [n, n] (lower triangle read), rhs [n].  Returns L
+        [n + 1, n] (rows < n: the factor's tiles left of the diagonal
+        64-blocks, which the kernels never store: zeros there; row n: z =
+        L^-1 rhs), V [T, 64, 64] (the inverses of the diagonal blocks), y [n]
+        (the solution), ok (False: a non-positive pivot was reported) and n."""
+        n = self.reduced_order()
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+        if S.shape != (n, n) or rhs.shape != (n,):
+            raise ValueError(f"debug_factor: the problem's reduced system has order {n}, got S {S.shape}, "
+                             f"rhs {rhs.shape}")
+        T = (n + 63) // 64
+        L, V, y = np.empty((n + 1, n)), np.empty((T, 64, 64)), np.empty(n)
+        ok = C.c_int(0)
+        self._check(self.lib.ba_debug_factor(self.h, _ptr(S), _ptr(rhs), _ptr(L), _ptr(V), _ptr(y), C.byref(ok)),
+                    "ba_debug_factor")
+        return {"L": L, "V": V, "y": y, "ok": bool(ok.value), "n": n}
+
     def covariance(self, cam_pairs=None, points=None) -> tuple[np.ndarray, np.ndarray]:
         """Marginal covariances at the current parameters (ba_covariance:
         ceres::Covariance with its defaults, (J^T J)^-1 over the variable

@@ -360,6 +360,41 @@ int ba_window_times(ba_ctx* ctx, double* ms, int n);
 int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double* Hcc, double* gc, double* S,
                     double* rhs, int* n_out);
 
+/* Test / inspection: run the DENSE_SCHUR factorisation + back substitution a
+ * solve's step runs (the context's own dispatch: whatever form the order and
+ * the BA_CHOL_* knobs select) on a caller-supplied system of the current
+ * problem's order n (= *n_out of ba_debug_blocks).
+ *   S_in[n*n]  row-major, lower triangle read (upper ignored); rhs_in[n]
+ *   L[(n+1)*n] row-major: rows < n the factor as the kernels leave it: the
+ *              tiles left of each row's diagonal 64-block.  The diagonal
+ *              64-blocks are NOT stored by the kernels (only their inverses
+ *              V leave the workgroup that factors them); they and everything
+ *              right of them come out as zeros, L_kk = V_k^-1 is the caller's
+ *              to rebuild.  Row n = z = L^-1 rhs.  (n % 64 == 0: the rhs row is
+ *              a tile row of its own and the kernels keep z's last block in
+ *              LDS; the entry forms those 64 values on the host as the back
+ *              substitution does, z_K = V_K A_{n,K}^T from the updated rhs
+ *              row.)
+ *   V[T*64*64] the explicit inverses of the diagonal blocks (T = ceil(n/64)),
+ *              lower triangular, identity past a partial last block's order;
+ *              the persistent form stores only the 16x16 blocks on and below
+ *              the block diagonal of a full 64-block (the rest is never read
+ *              and comes out as whatever the buffer held)
+ *   y[n]       the solution of S y = rhs
+ *   *ok        1, or 0 if the factorisation reported a non-positive pivot
+ *              (a normal outcome: the call still returns BA_OK)
+ * Any output pointer may be NULL.  The overlapped form, which builds S inside
+ * its own launch, cannot take an injected matrix and is never selected here.
+ * A hand-off spin bound is handled as in ba_covariance (one redo with the
+ * per-step launches, else BA_ERR_DEVICE).  Afterwards the context is as
+ * before the call: a ba_solve, ba_debug_blocks or ba_covariance on it is bit
+ * for bit what it would have been.
+ * Errors: BA_ERR_NO_PROBLEM before ba_set_problem; BA_ERR_INVALID_ARGUMENT
+ * for n == 0, a NULL input, a context with a communicator, or a system too
+ * large for DENSE_SCHUR. */
+int ba_debug_factor(ba_ctx* ctx, const double* S_in, const double* rhs_in, double* L, double* V, double* y,
+                    int* ok);
+
 /* Marginal covariances of parameter blocks at the current parameters:
  * ceres::Covariance with its defaults.  The covariance is (J^T J)^-1 with J
  * the Huber-corrected Jacobian ba_linearize returns, taken over the variable

@@ -22,8 +22,25 @@ def declared_functions():
 def test_header_declares_expected_entry_points():
     fns = declared_functions()
     for f in ("ba_create", "ba_destroy", "ba_set_problem", "ba_solve", "ba_get_params", "ba_eval_residuals",
-              "ba_last_error", "ba_comm_init"):
+              "ba_last_error", "ba_comm_init", "ba_debug_blocks", "ba_debug_factor", "ba_covariance"):
         assert f in fns
+
+
+def test_debug_factor_signature_matches_the_header():
+    """ba_debug_factor(ctx, S_in, rhs_in, L, V, y, ok): seven parameters, the
+    last an int*, an int status; a NULL context is refused without a device."""
+    txt = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    m = re.search(r"\bint\s+ba_debug_factor\s*\(([^)]*)\)\s*;", txt)
+    assert m, "prototype not found"
+    params = [p.strip() for p in m.group(1).split(",")]
+    assert len(params) == 7
+    assert params[0].startswith("ba_ctx*") and params[-1].replace(" ", "") == "int*ok"
+    assert all(p.startswith("const double*") for p in params[1:3])
+    assert all(p.startswith("double*") for p in params[3:6])
+    sig = {name: (res, args) for name, res, args in N.SIGNATURES}["ba_debug_factor"]
+    assert sig[0] is C.c_int and len(sig[1]) == 7 and sig[1][-1] is C.POINTER(C.c_int)
+    lib = N.load_library()
+    assert lib.ba_debug_factor(None, None, None, None, None, None, None) == 1   # BA_ERR_INVALID_ARGUMENT
 
 
 def test_library_exports_every_declared_symbol():
