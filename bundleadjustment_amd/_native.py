@@ -105,6 +105,15 @@ class ba_covariance_request(C.Structure):
     ]
 
 
+class ba_covariance_request_ex(C.Structure):
+    _fields_ = [
+        ("base", ba_covariance_request),
+        ("n_cam_pt", C.c_int32), ("n_pt_pairs", C.c_int32), ("cam_pt", C.c_void_p), ("cam_pt_cov", C.c_void_p),
+        ("pt_pairs", C.c_void_p), ("pt_pt_cov", C.c_void_p),
+        ("n_lev", C.c_int32), ("reserved", C.c_int32), ("lev_obs", C.c_void_p), ("leverage", C.c_void_p),
+    ]
+
+
 # int (*)(void* user, double* values, int64_t n, int op) of ba_comm_init_host
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int)
 
@@ -142,6 +151,7 @@ SIGNATURES = [
     ("ba_get_window_iteration_log", C.c_int, [C.c_void_p, C.c_int, C.POINTER(ba_iteration), C.c_int]),
     ("ba_window_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
+    ("ba_covariance_ex", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request_ex)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("ba_synchronize", C.c_int, [C.c_void_p]),
     ("ba_bench_iterations", C.c_int, [C.c_void_p, C.POINTER(ba_options), C.c_int, C.c_double,

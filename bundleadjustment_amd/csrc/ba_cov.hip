@@ -1,6 +1,7 @@
-// ba_cov.hip — marginal covariances from the dense Schur factor
-// (ba_covariance): what ceres::Covariance gives with its defaults, (J^T J)^-1
-// restricted to camera x camera and point x point blocks.
+// ba_cov.hip — covariances from the dense Schur factor (ba_covariance,
+// ba_covariance_ex): what ceres::Covariance gives with its defaults, blocks of
+// (J^T J)^-1 for any pair of cameras and points, and the leverages
+// J_o (J^T J)^-1 J_o^T of observations.
 //
 // Input is the state a DENSE_SCHUR factorisation of the undamped reduced
 // system leaves behind (ba_chol.hip): the off-diagonal 64 x 64 tiles L_ij of
@@ -173,13 +174,102 @@ __device__ __forceinline__ void cov_load_w(const DevProblem& P, const double* __
     for (int k = 0; k < 3; ++k) w[a * 3 + k] = c0[a] * r.r[9 + k] + c1[a] * r.r[12 + k];
 }
 
+// t = sum_{a in obs(p), b in obs(q)} W_a^T Sigma_scaled[c(a), c(b)] W_b (3 x 3,
+// row-major) by one wave; the sum is in lane 0.  Lane l takes the pairs (a, b)
+// with index l, l + 64, ... of obs(p) x obs(q) (increasing), then a fixed
+// reduction over the wave.  Observations by constant cameras have no camera
+// block and are skipped.
+__device__ __forceinline__ void cov_pair_sum(const DevProblem& P, const double* __restrict__ Sg,
+                                             const double* __restrict__ Wrec, int compact,
+                                             const double* __restrict__ scale_c, int p, int q, int lane,
+                                             double (&t)[9]) {
+  const size_t ld = (size_t)P.ld;
+  const int o0 = P.pt_off[p], m = P.pt_off[p + 1] - o0;
+  const int q0 = P.pt_off[q], mq = P.pt_off[q + 1] - q0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) t[k] = 0.0;
+  for (int e = lane; e < m * mq; e += 64) {
+    const int a = e / mq, b = e - a * mq;
+    const int va = P.obs_vc[o0 + a], vb = P.obs_vc[q0 + b];
+    if (va < 0 || vb < 0) continue;   // an observation by a constant camera: no camera block
+    double wa[18], wb[18];
+    cov_load_w(P, Wrec, compact != 0, scale_c, o0 + a, va, wa);
+    cov_load_w(P, Wrec, compact != 0, scale_c, q0 + b, vb, wb);
+    // Y = Sigma[va, vb] W_b (6 x 3), then t += W_a^T Y
+    double y[18];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const double g = cov_sym(Sg, ld, 6 * va + i, 6 * vb + j);
+        s0 += g * wb[j * 3];
+        s1 += g * wb[j * 3 + 1];
+        s2 += g * wb[j * 3 + 2];
+      }
+      y[i * 3] = s0; y[i * 3 + 1] = s1; y[i * 3 + 2] = s2;
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) s += wa[i * 3 + r] * y[i * 3 + c];
+        t[r * 3 + c] += s;
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) t[k] = wave_sum(t[k]);
+}
+
+// L_p^-1 (lower) and s_p of a variable point
+struct CovPt {
+  double li[3][3], s[3];
+  __device__ __forceinline__ void load(const double* __restrict__ Linv, const double* __restrict__ scale_p, int p,
+                                       size_t np) {
+    li[0][0] = Linv[p]; li[0][1] = 0.0; li[0][2] = 0.0;
+    li[1][0] = Linv[np + p]; li[1][1] = Linv[2 * np + p]; li[1][2] = 0.0;
+    li[2][0] = Linv[3 * np + p]; li[2][1] = Linv[4 * np + p]; li[2][2] = Linv[5 * np + p];
+    s[0] = scale_p[p]; s[1] = scale_p[np + p]; s[2] = scale_p[2 * np + p];
+  }
+};
+
+// dst (3 x 3, row-major) = s_p Lp^-T (eye I + t) Lq^-1 s_q: Cov(p, q) from the
+// sum of cov_pair_sum (eye = 1 for p == q: the point's marginal)
+__device__ __forceinline__ void cov_point_finish(const double (&t)[9], bool eye, const CovPt& cp, const CovPt& cq,
+                                                 double (&dst)[9]) {
+  double M[3][3], ML[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) M[r][c] = (eye && r == c ? 1.0 : 0.0) + t[r * 3 + c];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double x = 0.0;
+#pragma unroll
+      for (int l = c; l < 3; ++l) x += M[r][l] * cq.li[l][c];
+      ML[r][c] = x;
+    }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double x = 0.0;
+#pragma unroll
+      for (int l = r; l < 3; ++l) x += cp.li[l][r] * ML[l][c];
+      dst[r * 3 + c] = cp.s[r] * x * cq.s[c];
+    }
+}
+
 // Requested points, one per wave.  In scaled columns, with L_p the point's
 // 3 x 3 factor and W_a = E_a L_p^-T the records of its observations by
 // variable cameras,
 //   Sigma_pp = L_p^-T (I + sum_{a, b} W_a^T Sigma_scaled[c(a), c(b)] W_b) L_p^-1
-// and the result is s_p Sigma_pp s_p.  Lane l takes the pairs (a, b) with
-// index l, l + 64, ... of the point's observation list squared (increasing),
-// then a fixed xor reduction over the wave.  A constant point gives zeros.
+// and the result is s_p Sigma_pp s_p (cov_pair_sum, cov_point_finish).  A
+// constant point gives zeros.
 __global__ __launch_bounds__(256) void k_cov_points(DevProblem P, const double* __restrict__ Sg,
                                                     const double* __restrict__ Wrec, int compact,
                                                     const double* __restrict__ scale_c,
@@ -188,7 +278,6 @@ __global__ __launch_bounds__(256) void k_cov_points(DevProblem P, const double* 
                                                     int npts, double* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int wv = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), nwv = (int)((gridDim.x * blockDim.x) >> 6);
-  const size_t ld = (size_t)P.ld, np = (size_t)P.np;
   for (int q = wv; q < npts; q += nwv) {
     const int p = pts[q];
     double* dst = out + 9 * (size_t)q;
@@ -196,74 +285,323 @@ __global__ __launch_bounds__(256) void k_cov_points(DevProblem P, const double* 
       if (lane < 9) dst[lane] = 0.0;
       continue;
     }
+    double t[9];
+    cov_pair_sum(P, Sg, Wrec, compact, scale_c, p, p, lane, t);
+    if (lane == 0) {
+      CovPt cp;
+      cp.load(Linv, scale_p, p, (size_t)P.np);
+      double r[9];
+      cov_point_finish(t, true, cp, cp, r);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) dst[k] = r[k];
+    }
+  }
+}
+
+// Requested point pairs, one per wave: Cov(p, q) = s_p L_p^-T (delta_pq I +
+// sum_{a in obs(p), b in obs(q)} W_a^T Sigma_scaled[c(a), c(b)] W_b) L_q^-1 s_q.
+// The block is formed for (min, max) and stored transposed for p > q, so
+// Cov(p, q)^T and Cov(q, p) are the same bits; p == q is k_cov_points' sum and
+// finish, bit for bit.  A constant point gives zeros.
+__global__ __launch_bounds__(256) void k_cov_pt_pairs(DevProblem P, const double* __restrict__ Sg,
+                                                      const double* __restrict__ Wrec, int compact,
+                                                      const double* __restrict__ scale_c,
+                                                      const double* __restrict__ scale_p,
+                                                      const double* __restrict__ Linv, const int2* __restrict__ pq,
+                                                      int npairs, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int wv = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), nwv = (int)((gridDim.x * blockDim.x) >> 6);
+  for (int x = wv; x < npairs; x += nwv) {
+    const int2 r = pq[x];
+    const int p = min(r.x, r.y), q = max(r.x, r.y);
+    double* dst = out + 9 * (size_t)x;
+    if (!P.pt_var[p] || !P.pt_var[q]) {   // (uniform in the wave)
+      if (lane < 9) dst[lane] = 0.0;
+      continue;
+    }
+    double t[9];
+    cov_pair_sum(P, Sg, Wrec, compact, scale_c, p, q, lane, t);
+    if (lane == 0) {
+      CovPt cp, cq;
+      cp.load(Linv, scale_p, p, (size_t)P.np);
+      cq.load(Linv, scale_p, q, (size_t)P.np);
+      double v[9];
+      cov_point_finish(t, p == q, cp, cq, v);
+      const bool tr = r.x > r.y;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) dst[i * 3 + j] = tr ? v[j * 3 + i] : v[i * 3 + j];
+    }
+  }
+}
+
+// Requested (camera, point) cross blocks, one per wave:
+//   Cov(cam v, p) = s_v (-(sum_{a in obs(p)} Sigma_scaled[v, c(a)] W_a) L_p^-1) s_p   (6 x 3)
+// cp: {compact variable-camera index or -1 (constant camera), point}.  Lane l
+// takes row l & 7 (< 6) of the terms a = l >> 3, (l >> 3) + 8, ... in
+// increasing order, then a fixed xor reduction over the eight lanes of a row;
+// the row's lane applies L_p^-1, the scales and the sign.  A constant camera
+// or point gives zeros.
+__global__ __launch_bounds__(256) void k_cov_cam_pt(DevProblem P, const double* __restrict__ Sg,
+                                                    const double* __restrict__ Wrec, int compact,
+                                                    const double* __restrict__ scale_c,
+                                                    const double* __restrict__ scale_p,
+                                                    const double* __restrict__ Linv, const int2* __restrict__ cp,
+                                                    int nreq, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63, row = lane & 7, a0 = lane >> 3;
+  const int wv = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), nwv = (int)((gridDim.x * blockDim.x) >> 6);
+  const size_t ld = (size_t)P.ld;
+  for (int x = wv; x < nreq; x += nwv) {
+    const int v = cp[x].x, p = cp[x].y;
+    double* dst = out + 18 * (size_t)x;
+    if (v < 0 || !P.pt_var[p]) {   // (uniform in the wave)
+      if (lane < 18) dst[lane] = 0.0;
+      continue;
+    }
     const int o0 = P.pt_off[p], m = P.pt_off[p + 1] - o0;
+    double y0 = 0.0, y1 = 0.0, y2 = 0.0;
+    if (row < 6)
+      for (int a = a0; a < m; a += 8) {
+        const int va = P.obs_vc[o0 + a];
+        if (va < 0) continue;
+        double w[18];
+        cov_load_w(P, Wrec, compact != 0, scale_c, o0 + a, va, w);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          const double g = cov_sym(Sg, ld, 6 * v + row, 6 * va + j);
+          y0 += g * w[j * 3];
+          y1 += g * w[j * 3 + 1];
+          y2 += g * w[j * 3 + 2];
+        }
+      }
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) {
+      y0 += __shfl_xor(y0, off, 64);
+      y1 += __shfl_xor(y1, off, 64);
+      y2 += __shfl_xor(y2, off, 64);
+    }
+    if (lane < 6) {
+      CovPt c;
+      c.load(Linv, scale_p, p, (size_t)P.np);
+      const double y[3] = {y0, y1, y2};
+      const double sc = scale_c[(size_t)v * 6 + row];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        double s = 0.0;
+#pragma unroll
+        for (int l = k; l < 3; ++l) s += y[l] * c.li[l][k];
+        dst[row * 3 + k] = sc * -s * c.s[k];
+      }
+    }
+  }
+}
+
+// Leverages h_o = J_o Sigma J_o^T (2 x 2) of every observation of the listed
+// points, one point per workgroup of one wave.  With J_o = [Jc | Jp] of the
+// JR records (JA doubles per camera half), jc = Jc s_c, jp = Jp s_p and
+//   Y_a = sum_b Sigma_scaled[c(a), c(b)] W_b   (6 x 3, b over obs(p)),
+//   h_a = jc Sigma_scaled[c(a), c(a)] jc^T - (X + X^T) + Jp Sigma_pp Jp^T,
+//   X = jc Y_a L_p^-1 jp^T,   Sigma_pp = s_p L_p^-T (I + sum_a W_a^T Y_a) L_p^-1 s_p.
+// Lane l takes row l & 7 (< 6) of observation 8 g + (l >> 3) in round g.  The
+// W_b are staged in LDS 64 at a time (once per point up to 64 observations,
+// else once per round and chunk) and every lane sums its row of Y_a over b in
+// increasing order, so neither the number of observations of a point nor
+// duplicates are bounded; a lane's row of W_a comes from the staged chunk.  A round's products are reduced over the eight
+// lanes of an observation (xor 1, 2, 4) and, for sum_a W_a^T Y_a, over the
+// wave; the rounds add up in increasing order.  The first pass stores the
+// terms that need no Sigma_pp into hbuf [hoff[x] + a][4] (hoff: the running
+// count of observations of the listed points); the second
+// pass (same lane, so program order) adds Jp Sigma_pp Jp^T.  A constant
+// camera or point contributes nothing.
+constexpr int kLevLd = 19;   // LDS row stride of a staged W record
+__global__ __launch_bounds__(64) void k_cov_leverage(DevProblem P, const double* __restrict__ Sg,
+                                                     const double* __restrict__ Wrec, int compact,
+                                                     const double* __restrict__ scale_c,
+                                                     const double* __restrict__ scale_p,
+                                                     const double* __restrict__ Linv, const double* __restrict__ JR,
+                                                     int JA, const int* __restrict__ pts,
+                                                     const int* __restrict__ hoff, int npts, double* hbuf) {
+  __shared__ double Wst[64 * kLevLd];
+  __shared__ int vst[64];
+  const int lane = threadIdx.x, row = lane & 7, al = lane >> 3;
+  const size_t ld = (size_t)P.ld;
+  const double* JB = JR + (size_t)JA * P.no;
+  for (int x = blockIdx.x; x < npts; x += gridDim.x) {
+    const int p = pts[x];
+    const bool pvar = P.pt_var[p] != 0;
+    const int o0 = P.pt_off[p], m = P.pt_off[p + 1] - o0;
+    double* hp = hbuf + 4 * (size_t)hoff[x];   // this point's observations, in sorted order
+    CovPt c;
+    double jps[3] = {1.0, 1.0, 1.0};
+    if (pvar) {
+      c.load(Linv, scale_p, p, (size_t)P.np);
+      jps[0] = c.s[0]; jps[1] = c.s[1]; jps[2] = c.s[2];
+    }
     double t[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) t[k] = 0.0;
-    for (int e = lane; e < m * m; e += 64) {
-      const int a = e / m, b = e - a * m;
-      const int va = P.obs_vc[o0 + a], vb = P.obs_vc[o0 + b];
-      if (va < 0 || vb < 0) continue;   // an observation by a constant camera: no camera block
-      double wa[18], wb[18];
-      cov_load_w(P, Wrec, compact != 0, scale_c, o0 + a, va, wa);
-      cov_load_w(P, Wrec, compact != 0, scale_c, o0 + b, vb, wb);
-      // Y = Sigma[va, vb] W_b (6 x 3), then t += W_a^T Y
-      double y[18];
+    // W_b, b in [b0, b0 + nb), into LDS (between two barriers)
+    auto stage = [&](int b0, int nb) {
+      __syncthreads();   // (the last chunk's readers are done)
+      if (lane < nb) {
+        const int vb = P.obs_vc[o0 + b0 + lane];
+        vst[lane] = vb;
+        if (vb >= 0) {
+          double w[18];
+          cov_load_w(P, Wrec, compact != 0, scale_c, o0 + b0 + lane, vb, w);
 #pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+          for (int k = 0; k < 18; ++k) Wst[lane * kLevLd + k] = w[k];
+        }
+      }
+      __syncthreads();
+    };
+    const bool one = m <= 64;   // a single chunk: staged once for all rounds
+    if (pvar && one) stage(0, m);
+    for (int a8 = 0; a8 < m; a8 += 8) {
+      const int a = a8 + al;
+      const int va = (a < m && row < 6) ? P.obs_vc[o0 + a] : -1;
+      double y[3] = {0.0, 0.0, 0.0}, wr[3] = {0.0, 0.0, 0.0};
+      if (pvar)
+        for (int b0 = 0; b0 < m; b0 += 64) {
+          const int nb = min(64, m - b0);
+          if (!one) stage(b0, nb);
+          if (va < 0) continue;
+          if (a8 >= b0 && a8 < b0 + 64) {   // (a round lies inside one chunk) row `row` of W_a
+#pragma unroll
+            for (int k = 0; k < 3; ++k) wr[k] = Wst[(a - b0) * kLevLd + row * 3 + k];
+          }
+          for (int b = 0; b < nb; ++b) {
+            const int vb = vst[b];
+            if (vb < 0) continue;
+            const double* w = &Wst[b * kLevLd];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+              const double g = cov_sym(Sg, ld, 6 * va + row, 6 * vb + j);
+              y[0] += g * w[j * 3];
+              y[1] += g * w[j * 3 + 1];
+              y[2] += g * w[j * 3 + 2];
+            }
+          }
+        }
+      // this lane's terms: row `row` of W_a and of jc; 4 + 6 + 9 products
+      double cc[4] = {0.0, 0.0, 0.0, 0.0}, gy[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, tt[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) tt[k] = 0.0;
+      if (va >= 0) {
+        const double* ja = JR + (size_t)(o0 + a) * JA;
+        double jc[2][6];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+          for (int j = 0; j < 6; ++j) jc[r][j] = ja[r * 6 + j] * scale_c[(size_t)va * 6 + j];
+        double z0 = 0.0, z1 = 0.0, j0 = 0.0, j1 = 0.0;
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
-          const double g = cov_sym(Sg, ld, 6 * va + i, 6 * vb + j);
-          s0 += g * wb[j * 3];
-          s1 += g * wb[j * 3 + 1];
-          s2 += g * wb[j * 3 + 2];
+          const double g = cov_sym(Sg, ld, 6 * va + row, 6 * va + j);
+          z0 += g * jc[0][j];
+          z1 += g * jc[1][j];
+          if (j == row) { j0 = jc[0][j]; j1 = jc[1][j]; }
         }
-        y[i * 3] = s0; y[i * 3 + 1] = s1; y[i * 3 + 2] = s2;
+        cc[0] = j0 * z0; cc[1] = j0 * z1; cc[2] = j1 * z0; cc[3] = j1 * z1;
+        if (pvar) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            gy[k] = j0 * y[k];
+            gy[3 + k] = j1 * y[k];
+#pragma unroll
+            for (int l = 0; l < 3; ++l) tt[k * 3 + l] = wr[k] * y[l];
+          }
+        }
       }
 #pragma unroll
-      for (int r = 0; r < 3; ++r)
+      for (int off = 1; off < 8; off <<= 1) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
+        for (int k = 0; k < 4; ++k) cc[k] += __shfl_xor(cc[k], off, 64);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) gy[k] += __shfl_xor(gy[k], off, 64);
+      }
+      if (pvar) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+          double s = tt[k];
+#pragma unroll
+          for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off, 64);
+          t[k] += s;
+        }
+      }
+      if (row == 0 && a < m) {
+        double h00 = cc[0], h01 = 0.5 * (cc[1] + cc[2]), h11 = cc[3];
+        if (pvar) {
+          // X = (jc Y_a) L_p^-1 jp^T
+          const double* jb = JB + (size_t)(o0 + a) * 8;
+          double gl[2][3], X[2][2];
+#pragma unroll
+          for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+              double s = 0.0;
+#pragma unroll
+              for (int l = k; l < 3; ++l) s += gy[r * 3 + l] * c.li[l][k];
+              gl[r][k] = s;
+            }
+#pragma unroll
+          for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+              double s = 0.0;
+#pragma unroll
+              for (int k = 0; k < 3; ++k) s += gl[r][k] * (jb[q * 3 + k] * jps[k]);
+              X[r][q] = s;
+            }
+          h00 -= X[0][0] + X[0][0];
+          h01 -= X[0][1] + X[1][0];
+          h11 -= X[1][1] + X[1][1];
+        }
+        double* h = hp + 4 * (size_t)a;
+        h[0] = h00; h[1] = h01; h[2] = h01; h[3] = h11;
+      }
+    }
+    if (!pvar) continue;
+    double spp[9];
+    cov_point_finish(t, true, c, c, spp);   // (every lane holds the same t)
+    for (int a8 = 0; a8 < m; a8 += 8) {
+      const int a = a8 + al;
+      if (row != 0 || a >= m) continue;
+      const double* jb = JB + (size_t)(o0 + a) * 8;
+      double js[2][3];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
           double s = 0.0;
 #pragma unroll
-          for (int i = 0; i < 6; ++i) s += wa[i * 3 + r] * y[i * 3 + c];
-          t[r * 3 + c] += s;
+          for (int l = 0; l < 3; ++l) s += jb[r * 3 + l] * spp[l * 3 + k];
+          js[r][k] = s;
         }
-    }
+      double q[2][2];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) t[k] = wave_sum(t[k]);
-    if (lane == 0) {
-      // M = I + t; R = Li^T M Li with Li = L_p^-1 (lower); out = s R s
-      const double li[3][3] = {{Linv[p], 0.0, 0.0},
-                               {Linv[np + p], Linv[2 * np + p], 0.0},
-                               {Linv[3 * np + p], Linv[4 * np + p], Linv[5 * np + p]}};
-      const double s[3] = {scale_p[p], scale_p[np + p], scale_p[2 * np + p]};
-      double M[3][3], ML[3][3];
+      for (int r = 0; r < 2; ++r)
 #pragma unroll
-      for (int r = 0; r < 3; ++r)
+        for (int u = 0; u < 2; ++u) {
+          double s = 0.0;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) M[r][c] = (r == c ? 1.0 : 0.0) + t[r * 3 + c];
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          double x = 0.0;
-#pragma unroll
-          for (int l = c; l < 3; ++l) x += M[r][l] * li[l][c];
-          ML[r][c] = x;
+          for (int k = 0; k < 3; ++k) s += js[r][k] * jb[u * 3 + k];
+          q[r][u] = s;
         }
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          double x = 0.0;
-#pragma unroll
-          for (int l = r; l < 3; ++l) x += li[l][r] * ML[l][c];
-          dst[r * 3 + c] = s[r] * x * s[c];
-        }
+      double* h = hp + 4 * (size_t)a;
+      const double h01 = h[1] + 0.5 * (q[0][1] + q[1][0]);
+      h[0] += q[0][0]; h[1] = h01; h[2] = h01; h[3] += q[1][1];
     }
   }
+}
+
+// out[x] = hbuf[idx[x]] (2 x 2): the request's order, repeats included
+__global__ __launch_bounds__(256) void k_cov_lev_gather(const double* __restrict__ hbuf, const int* __restrict__ idx,
+                                                        int n, double* __restrict__ out) {
+  const size_t total = 4 * (size_t)n;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x)
+    out[e] = hbuf[4 * (size_t)idx[e >> 2] + (e & 3)];
 }
 
 // U = L^-T into W.S, then Sigma_scaled into the lower block tiles of W.Lf
@@ -288,6 +626,34 @@ void launch_cov_points(const DevProblem& P, const DevWork& W, const int* pts, in
   hipLaunchKernelGGL(k_cov_points, dim3(grid), dim3(256), 0, s, P, (const double*)W.Lf, (const double*)W.W,
                      W.wcompact ? 1 : 0, (const double*)W.scale_c, (const double*)W.scale_p, (const double*)W.Linv, pts,
                      npts, out);
+}
+
+void launch_cov_pt_pairs(const DevProblem& P, const DevWork& W, const int2* pq, int npairs, double* out,
+                         hipStream_t s) {
+  if (npairs == 0) return;
+  const int grid = std::min(kMaxBlocks, (npairs + 3) / 4);
+  hipLaunchKernelGGL(k_cov_pt_pairs, dim3(grid), dim3(256), 0, s, P, (const double*)W.Lf, (const double*)W.W,
+                     W.wcompact ? 1 : 0, (const double*)W.scale_c, (const double*)W.scale_p, (const double*)W.Linv, pq,
+                     npairs, out);
+}
+
+void launch_cov_cam_pt(const DevProblem& P, const DevWork& W, const int2* cp, int nreq, double* out, hipStream_t s) {
+  if (nreq == 0) return;
+  const int grid = std::min(kMaxBlocks, (nreq + 3) / 4);
+  hipLaunchKernelGGL(k_cov_cam_pt, dim3(grid), dim3(256), 0, s, P, (const double*)W.Lf, (const double*)W.W,
+                     W.wcompact ? 1 : 0, (const double*)W.scale_c, (const double*)W.scale_p, (const double*)W.Linv, cp,
+                     nreq, out);
+}
+
+void launch_cov_leverage(const DevProblem& P, const DevWork& W, const int* pts, const int* hoff, int npts,
+                         double* hbuf, const int* idx, int nlev, double* out, hipStream_t s) {
+  if (nlev == 0) return;
+  if (npts > 0)
+    hipLaunchKernelGGL(k_cov_leverage, dim3(std::min(npts, 1 << 20)), dim3(64), 0, s, P, (const double*)W.Lf,
+                       (const double*)W.W, W.wcompact ? 1 : 0, (const double*)W.scale_c, (const double*)W.scale_p,
+                       (const double*)W.Linv, (const double*)W.JR, jr_ja_host(P.nc), pts, hoff, npts, hbuf);
+  hipLaunchKernelGGL(k_cov_lev_gather, dim3(grid_for(std::min(nlev, 1 << 24) * 4)), dim3(256), 0, s,
+                     (const double*)hbuf, idx, nlev, out);
 }
 
 }  // namespace bahip

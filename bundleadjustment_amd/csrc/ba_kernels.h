@@ -250,6 +250,16 @@ void launch_cov_cam_blocks(const DevProblem& P, const DevWork& W, const int2* pa
                            hipStream_t s);
 // pts: point indices; out [npts][9] (zeros for a constant point)
 void launch_cov_points(const DevProblem& P, const DevWork& W, const int* pts, int npts, double* out, hipStream_t s);
+// pq: point index pairs; out [npairs][9] = Cov(p, q) (zeros with a constant point; p == q: launch_cov_points' bits)
+void launch_cov_pt_pairs(const DevProblem& P, const DevWork& W, const int2* pq, int npairs, double* out,
+                         hipStream_t s);
+// cp: {compact variable-camera index or -1, point index}; out [nreq][18] = Cov(cam, point), 6 x 3
+void launch_cov_cam_pt(const DevProblem& P, const DevWork& W, const int2* cp, int nreq, double* out, hipStream_t s);
+// leverages J_o Sigma J_o^T of every observation of the points pts (each
+// once) from the J records in W.JR (launch_linearize_jr): observation a of
+// pts[x] into hbuf[hoff[x] + a][4]; then out[x] = hbuf[idx[x]], x < nlev
+void launch_cov_leverage(const DevProblem& P, const DevWork& W, const int* pts, const int* hoff, int npts,
+                         double* hbuf, const int* idx, int nlev, double* out, hipStream_t s);
 bool obs_w_pc_ok(const DevProblem& P, const DevWork& W);   // k_obs_w_rc has the PCG record form for this source
 bool chol_persist_fits(int device, int n);   // every workgroup of k_chol_persist resident at once
 void chol_split_tasks(int n, std::vector<int4>& tasks, std::vector<int>& off);   // the split form's task table

@@ -1351,39 +1351,85 @@ void get_params(ba_ctx* ctx, double* cams, double* pts) {
 }
 
 // ---------------------------------------------------------------------------
-// ceres::Covariance (defaults) for camera x camera and point x point blocks:
-// the undamped reduced system through a DENSE_SCHUR step's own passes and
-// factorisation, then ba_cov.hip
+// ceres::Covariance (defaults) for any pair of parameter blocks, and the
+// leverages J_o Sigma J_o^T of observations (ba_covariance, ba_covariance_ex;
+// fn: the entry point's name for messages): the undamped reduced system
+// through a DENSE_SCHUR step's own passes and factorisation, then ba_cov.hip
 // ---------------------------------------------------------------------------
-void covariance(ba_ctx* ctx, const ba_covariance_request* req) {
-  if (!req) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: request is NULL"};
-  if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, "ba_covariance before ba_set_problem"};
+void covariance(ba_ctx* ctx, const ba_covariance_request_ex* rx, const std::string& fn) {
+  if (!rx) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": request is NULL"};
+  const ba_covariance_request* req = &rx->base;
+  if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, fn + " before ba_set_problem"};
   if (ctx->has_comm())
-    throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: not available on a context with a communicator"};
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": not available on a context with a communicator"};
   const int m = req->n_cam_pairs, k = req->n_points;
-  if (m < 0 || k < 0 || (m > 0 && (!req->cam_pairs || !req->cam_cov)) || (k > 0 && (!req->points || !req->pt_cov)))
-    throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: bad sizes or missing array"};
-  std::vector<int2> pairs_h(m);
-  for (int q = 0; q < m; ++q) {
-    int v[2];
-    for (int h = 0; h < 2; ++h) {
-      const int c = req->cam_pairs[2 * q + h];
-      if (c < 0 || c >= ctx->nc)
-        throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: camera index " + std::to_string(c) + " out of range"};
-      v[h] = ctx->h_vc[c];
-      if (v[h] < 0 && !ctx->cam_fixed_h[c])
-        throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: camera " + std::to_string(c) +
-                                                   " is variable but has no observation"};
-    }
-    pairs_h[q] = make_int2(v[0], v[1]);
-  }
-  for (int q = 0; q < k; ++q) {
-    const int p = req->points[q];
-    if (p < 0 || p >= ctx->np)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: point index " + std::to_string(p) + " out of range"};
-    if (!ctx->h_pt_var[p] && !ctx->pt_fixed_h[p])
-      throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: point " + std::to_string(p) +
+  const int ncp = rx->n_cam_pt, npp = rx->n_pt_pairs, nlev = rx->n_lev;
+  if (m < 0 || k < 0 || (m > 0 && (!req->cam_pairs || !req->cam_cov)) || (k > 0 && (!req->points || !req->pt_cov)) ||
+      ncp < 0 || npp < 0 || nlev < 0 || (ncp > 0 && (!rx->cam_pt || !rx->cam_pt_cov)) ||
+      (npp > 0 && (!rx->pt_pairs || !rx->pt_pt_cov)) || (nlev > 0 && !rx->leverage) ||
+      (nlev > 0 && !rx->lev_obs && nlev != ctx->no))
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": bad sizes or missing array"};
+  // compact index of a requested camera (-1: constant), point checks
+  auto cam_index = [&](int c) {
+    if (c < 0 || c >= ctx->nc)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": camera index " + std::to_string(c) + " out of range"};
+    const int v = ctx->h_vc[c];
+    if (v < 0 && !ctx->cam_fixed_h[c])
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": camera " + std::to_string(c) +
                                                  " is variable but has no observation"};
+    return v;
+  };
+  auto check_point = [&](int p) {
+    if (p < 0 || p >= ctx->np)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": point index " + std::to_string(p) + " out of range"};
+    if (!ctx->h_pt_var[p] && !ctx->pt_fixed_h[p])
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": point " + std::to_string(p) +
+                                                 " is variable but has no observation"};
+  };
+  std::vector<int2> pairs_h(m), cp_h(ncp);
+  for (int q = 0; q < m; ++q) {
+    const int v0 = cam_index(req->cam_pairs[2 * q]), v1 = cam_index(req->cam_pairs[2 * q + 1]);
+    pairs_h[q] = make_int2(v0, v1);
+  }
+  for (int q = 0; q < k; ++q) check_point(req->points[q]);
+  for (int q = 0; q < ncp; ++q) {
+    const int v = cam_index(rx->cam_pt[2 * q]);
+    check_point(rx->cam_pt[2 * q + 1]);
+    cp_h[q] = make_int2(v, rx->cam_pt[2 * q + 1]);
+  }
+  for (int q = 0; q < 2 * npp; ++q) check_point(rx->pt_pairs[q]);
+  // leverages: the points that have a requested observation (increasing,
+  // each once), the running count of their observations (a point's slots in
+  // the result scratch) and the scratch slot of each requested observation
+  std::vector<int> lev_idx(nlev), lev_pts, lev_off;
+  size_t lev_slots = 0;
+  if (nlev > 0) {
+    const int no = ctx->no;
+    const std::vector<int>& off = ctx->h_pt_off;
+    if (!rx->lev_obs) {   // every observation: the inverse of perm, every observed point
+      for (int s = 0; s < no; ++s) lev_idx[ctx->perm[s]] = s;
+      for (int p = 0; p < ctx->np; ++p)
+        if (off[p + 1] > off[p]) { lev_pts.push_back(p); lev_off.push_back(off[p]); }
+      lev_slots = (size_t)no;
+    } else {
+      std::vector<int> inv(no), pt_of(nlev), slot0(ctx->np, -1);
+      for (int s = 0; s < no; ++s) inv[ctx->perm[s]] = s;
+      for (int q = 0; q < nlev; ++q) {
+        const int o = rx->lev_obs[q];
+        if (o < 0 || o >= no)
+          throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": observation index " + std::to_string(o) + " out of range"};
+        pt_of[q] = (int)(std::upper_bound(off.begin(), off.end(), inv[o]) - off.begin()) - 1;
+        slot0[pt_of[q]] = 0;
+      }
+      for (int p = 0; p < ctx->np; ++p)
+        if (slot0[p] == 0) {
+          slot0[p] = (int)lev_slots;
+          lev_pts.push_back(p);
+          lev_off.push_back((int)lev_slots);
+          lev_slots += (size_t)(off[p + 1] - off[p]);
+        }
+      for (int q = 0; q < nlev; ++q) lev_idx[q] = slot0[pt_of[q]] + inv[rx->lev_obs[q]] - off[pt_of[q]];
+    }
   }
   HIP_OK(hipSetDevice(ctx->device));
   ba_options o;
@@ -1397,12 +1443,20 @@ void covariance(ba_ctx* ctx, const ba_covariance_request* req) {
   for (hipEvent_t& x : ev.e) HIP_OK(hipEventCreate(&x));
   HIP_OK(hipEventRecord(ev.e[0], s));
   const LinResult L = linearize(ctx, true, o.min_lm_diagonal, o.max_lm_diagonal);
-  if (!L.ok) throw BaError{BA_ERR_SINGULAR, "ba_covariance: the linearisation is not finite"};
+  if (!L.ok) throw BaError{BA_ERR_SINGULAR, fn + ": the linearisation is not finite"};
+  DevWork& W = ctx->W;
+  if (nlev > 0 && W.jrfree) {
+    // the iteration never stores J: write the records for the leverage pass,
+    // as ba_linearize does for its read-back (its cost partials are not this
+    // call's: fold and clear them so no later reduction counts them)
+    if (!W.JR) W.JR = ctx->dalloc<double>((size_t)(bahip::jr_ja_host(ctx->P.nc) + 8) * ctx->no);
+    bahip::launch_linearize_jr(ctx->P, W, s);
+    launch_reduce(W, bit(SL_COST) | bit(SL_LIN_BAD), 0, s);
+  }
   step_w_storage(ctx, o);
   // an infinite radius: every D = sqrt(diag / radius) of the LM diagonal is
   // exactly zero, so the step's passes form the undamped system
   const double radius = std::numeric_limits<double>::infinity();
-  DevWork& W = ctx->W;
   for (int attempt = 0;; ++attempt) {
     form_reduced_dense(ctx, radius, false);   // (ensure_dense refuses a system too large for DENSE_SCHUR)
     HIP_OK(hipEventRecord(ev.e[1], s));
@@ -1420,34 +1474,63 @@ void covariance(ba_ctx* ctx, const ba_covariance_request* req) {
       continue;
     }
     if (h[SL_ELIM_BAD] != 0.0)
-      throw BaError{BA_ERR_SINGULAR, "ba_covariance: " + std::to_string((long long)h[SL_ELIM_BAD]) +
+      throw BaError{BA_ERR_SINGULAR, fn + ": " + std::to_string((long long)h[SL_ELIM_BAD]) +
                                          " point block(s) not positive definite"};
     if (ctx->n > 0 && h[SL_CHOL_BAD] != 0.0)
-      throw BaError{BA_ERR_SINGULAR, "ba_covariance: the reduced camera system is not positive definite"};
+      throw BaError{BA_ERR_SINGULAR, fn + ": the reduced camera system is not positive definite"};
     break;
   }
   // request and result staging (freed on every exit)
+  enum { D_PAIRS, D_CAM, D_PTS, D_PT, D_CP, D_CPOUT, D_PQ, D_PQOUT, D_LPTS, D_LOFF, D_LIDX, D_HBUF, D_LEV, D_N };
   struct Dev {
-    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* p[D_N] = {};
     ~Dev() { for (void* x : p) if (x) (void)hipFree(x); }
   } d;
+  auto stage = [&](int slot, const void* src, size_t bytes) {
+    HIP_OK(hipMalloc(&d.p[slot], bytes));
+    if (src) HIP_OK(hipMemcpyAsync(d.p[slot], src, bytes, hipMemcpyHostToDevice, s));
+  };
   if (m > 0) {
-    HIP_OK(hipMalloc(&d.p[0], sizeof(int2) * (size_t)m));
-    HIP_OK(hipMalloc(&d.p[1], sizeof(double) * 36 * (size_t)m));
-    HIP_OK(hipMemcpyAsync(d.p[0], pairs_h.data(), sizeof(int2) * (size_t)m, hipMemcpyHostToDevice, s));
+    stage(D_PAIRS, pairs_h.data(), sizeof(int2) * (size_t)m);
+    stage(D_CAM, nullptr, sizeof(double) * 36 * (size_t)m);
   }
   if (k > 0) {
-    HIP_OK(hipMalloc(&d.p[2], sizeof(int) * (size_t)k));
-    HIP_OK(hipMalloc(&d.p[3], sizeof(double) * 9 * (size_t)k));
-    HIP_OK(hipMemcpyAsync(d.p[2], req->points, sizeof(int) * (size_t)k, hipMemcpyHostToDevice, s));
+    stage(D_PTS, req->points, sizeof(int) * (size_t)k);
+    stage(D_PT, nullptr, sizeof(double) * 9 * (size_t)k);
+  }
+  if (ncp > 0) {
+    stage(D_CP, cp_h.data(), sizeof(int2) * (size_t)ncp);
+    stage(D_CPOUT, nullptr, sizeof(double) * 18 * (size_t)ncp);
+  }
+  if (npp > 0) {
+    stage(D_PQ, rx->pt_pairs, sizeof(int2) * (size_t)npp);
+    stage(D_PQOUT, nullptr, sizeof(double) * 9 * (size_t)npp);
+  }
+  if (nlev > 0) {
+    stage(D_LPTS, lev_pts.data(), sizeof(int) * lev_pts.size());
+    stage(D_LOFF, lev_off.data(), sizeof(int) * lev_off.size());
+    stage(D_LIDX, lev_idx.data(), sizeof(int) * (size_t)nlev);
+    stage(D_HBUF, nullptr, sizeof(double) * 4 * lev_slots);
+    stage(D_LEV, nullptr, sizeof(double) * 4 * (size_t)nlev);
   }
   launch_cov_inverse(ctx->P, W, s);
   HIP_OK(hipEventRecord(ev.e[3], s));
-  launch_cov_cam_blocks(ctx->P, W, static_cast<const int2*>(d.p[0]), m, static_cast<double*>(d.p[1]), s);
-  launch_cov_points(ctx->P, W, static_cast<const int*>(d.p[2]), k, static_cast<double*>(d.p[3]), s);
+  launch_cov_cam_blocks(ctx->P, W, static_cast<const int2*>(d.p[D_PAIRS]), m, static_cast<double*>(d.p[D_CAM]), s);
+  launch_cov_points(ctx->P, W, static_cast<const int*>(d.p[D_PTS]), k, static_cast<double*>(d.p[D_PT]), s);
+  launch_cov_cam_pt(ctx->P, W, static_cast<const int2*>(d.p[D_CP]), ncp, static_cast<double*>(d.p[D_CPOUT]), s);
+  launch_cov_pt_pairs(ctx->P, W, static_cast<const int2*>(d.p[D_PQ]), npp, static_cast<double*>(d.p[D_PQOUT]), s);
+  launch_cov_leverage(ctx->P, W, static_cast<const int*>(d.p[D_LPTS]), static_cast<const int*>(d.p[D_LOFF]),
+                      (int)lev_pts.size(), static_cast<double*>(d.p[D_HBUF]), static_cast<const int*>(d.p[D_LIDX]), nlev,
+                      static_cast<double*>(d.p[D_LEV]), s);
   HIP_OK(hipGetLastError());
-  if (m > 0) HIP_OK(hipMemcpyAsync(req->cam_cov, d.p[1], sizeof(double) * 36 * (size_t)m, hipMemcpyDeviceToHost, s));
-  if (k > 0) HIP_OK(hipMemcpyAsync(req->pt_cov, d.p[3], sizeof(double) * 9 * (size_t)k, hipMemcpyDeviceToHost, s));
+  auto fetch = [&](double* dst, int slot, size_t count) {
+    if (count > 0) HIP_OK(hipMemcpyAsync(dst, d.p[slot], sizeof(double) * count, hipMemcpyDeviceToHost, s));
+  };
+  fetch(req->cam_cov, D_CAM, 36 * (size_t)m);
+  fetch(req->pt_cov, D_PT, 9 * (size_t)k);
+  fetch(rx->cam_pt_cov, D_CPOUT, 18 * (size_t)ncp);
+  fetch(rx->pt_pt_cov, D_PQOUT, 9 * (size_t)npp);
+  fetch(rx->leverage, D_LEV, 4 * (size_t)nlev);
   // W.S held L^-T: back to zeros, its state before the first step (the
   // steps rewrite its lower triangle only)
   if (ctx->n > 0) HIP_OK(hipMemsetAsync(W.S, 0, sizeof(double) * (size_t)(ctx->n + 1) * std::max(ctx->ld, 1), s));
@@ -1455,11 +1538,20 @@ void covariance(ba_ctx* ctx, const ba_covariance_request* req) {
   HIP_OK(hipStreamSynchronize(s));
   for (size_t i = 0; i < 36 * (size_t)m; ++i)
     if (!std::isfinite(req->cam_cov[i]))
-      throw BaError{BA_ERR_SINGULAR, "ba_covariance: camera block " + std::to_string(i / 36) + " is not finite"};
+      throw BaError{BA_ERR_SINGULAR, fn + ": camera block " + std::to_string(i / 36) + " is not finite"};
   for (size_t i = 0; i < 9 * (size_t)k; ++i)
     if (!std::isfinite(req->pt_cov[i]))
-      throw BaError{BA_ERR_SINGULAR, "ba_covariance: the block of point " + std::to_string(req->points[i / 9]) +
+      throw BaError{BA_ERR_SINGULAR, fn + ": the block of point " + std::to_string(req->points[i / 9]) +
                                          " is not finite"};
+  for (size_t i = 0; i < 18 * (size_t)ncp; ++i)
+    if (!std::isfinite(rx->cam_pt_cov[i]))
+      throw BaError{BA_ERR_SINGULAR, fn + ": camera-point block " + std::to_string(i / 18) + " is not finite"};
+  for (size_t i = 0; i < 9 * (size_t)npp; ++i)
+    if (!std::isfinite(rx->pt_pt_cov[i]))
+      throw BaError{BA_ERR_SINGULAR, fn + ": point-point block " + std::to_string(i / 9) + " is not finite"};
+  for (size_t i = 0; i < 4 * (size_t)nlev; ++i)
+    if (!std::isfinite(rx->leverage[i]))
+      throw BaError{BA_ERR_SINGULAR, fn + ": leverage " + std::to_string(i / 4) + " is not finite"};
   ctx->cov_ms.assign(4, 0.0);
   for (int i = 0; i < 4; ++i) {
     float ms = 0.0f;
@@ -2200,9 +2292,19 @@ int ba_debug_factor(ba_ctx* ctx, const double* S_in, const double* rhs_in, doubl
   return guarded(ctx, [&] { debug_factor(ctx, S_in, rhs_in, L, V, y, ok); });
 }
 
+int ba_covariance_ex(ba_ctx* ctx, const ba_covariance_request_ex* req) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { covariance(ctx, req, "ba_covariance_ex"); });
+}
+
 int ba_covariance(ba_ctx* ctx, const ba_covariance_request* req) {
   if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] { covariance(ctx, req); });
+  return guarded(ctx, [&] {
+    if (!req) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_covariance: request is NULL"};
+    ba_covariance_request_ex rx{};   // the same implementation, nothing else requested
+    rx.base = *req;
+    covariance(ctx, &rx, "ba_covariance");
+  });
 }
 
 int ba_covariance_times(ba_ctx* ctx, double* ms, int n) {

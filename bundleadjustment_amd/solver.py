@@ -276,8 +276,39 @@ class Solver:
         self._check(self.lib.ba_covariance(self.h, C.byref(req)), "ba_covariance")
         return cam_cov, pt_cov
 
+    def covariance_ex(self, cam_pairs=None, points=None, cam_pt=None, pt_pairs=None, leverage_obs=None) -> dict:
+        """Any covariance block and observation leverages from one
+        factorisation (ba_covariance_ex).  cam_pairs [m, 2] and points [k] as
+        in covariance(), except that None requests nothing; cam_pt [a, 2]:
+        (camera, point) pairs; pt_pairs [b, 2]: point pairs (p, q), p == q
+        allowed; leverage_obs [l]: observation indices, or "all" for every
+        observation in the problem's order.  Returns a dict of arrays:
+        cam_cov [m, 6, 6], pt_cov [k, 3, 3], cam_pt_cov [a, 6, 3] =
+        Cov(cam, pt), pt_pt_cov [b, 3, 3] = Cov(p, q), leverage [l, 2, 2] =
+        J_o Sigma J_o^T.  Blocks of constant cameras / points are zero."""
+        def idx(a, cols):
+            a = np.ascontiguousarray(a if a is not None else [], dtype=np.int32)
+            return a.reshape(-1, cols) if cols > 1 else a.reshape(-1)
+        cp, pt, cq, pq = idx(cam_pairs, 2), idx(points, 1), idx(cam_pt, 2), idx(pt_pairs, 2)
+        every = isinstance(leverage_obs, str)
+        if every and leverage_obs != "all":
+            raise ValueError(f"covariance_ex: leverage_obs = {leverage_obs!r}")
+        lo = None if every else idx(leverage_obs, 1)
+        n_lev = self.problem.n_obs if every else lo.size
+        out = {"cam_cov": np.empty((cp.shape[0], 6, 6)), "pt_cov": np.empty((pt.size, 3, 3)),
+               "cam_pt_cov": np.empty((cq.shape[0], 6, 3)), "pt_pt_cov": np.empty((pq.shape[0], 3, 3)),
+               "leverage": np.empty((n_lev, 2, 2))}
+        base = N.ba_covariance_request(n_cam_pairs=cp.shape[0], n_points=pt.size, cam_pairs=_ptr(cp),
+                                       cam_cov=_ptr(out["cam_cov"]), points=_ptr(pt), pt_cov=_ptr(out["pt_cov"]))
+        req = N.ba_covariance_request_ex(base=base, n_cam_pt=cq.shape[0], n_pt_pairs=pq.shape[0], cam_pt=_ptr(cq),
+                                         cam_pt_cov=_ptr(out["cam_pt_cov"]), pt_pairs=_ptr(pq),
+                                         pt_pt_cov=_ptr(out["pt_pt_cov"]), n_lev=n_lev, reserved=0,
+                                         lev_obs=_ptr(lo), leverage=_ptr(out["leverage"]))
+        self._check(self.lib.ba_covariance_ex(self.h, C.byref(req)), "ba_covariance_ex")
+        return out
+
     def covariance_times(self) -> np.ndarray:
-        """Device time (ms) of the phases of the last covariance() call:
+        """Device time (ms) of the phases of the last covariance() / covariance_ex() call:
         linearisation + reduced system, factorisation, inverse, gathers."""
         n = self.lib.ba_covariance_times(self.h, None, 0)
         out = np.empty(max(n, 0))

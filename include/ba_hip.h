@@ -405,7 +405,7 @@ int ba_debug_factor(ba_ctx* ctx, const double* S_in, const double* rhs_in, doubl
  *   point p  Hpp_p^-1 + Hpp_p^-1 (sum_{a,b in obs(p)} Hpc_a Sigma[c(a), c(b)]
  *            Hcp_b) Hpp_p^-1, 3x3.
  * Every block of a constant camera or constant point is all zeros, as in
- * Ceres.  Camera-point cross blocks are not available.
+ * Ceres.  Camera-point and point-point cross blocks: ba_covariance_ex.
  *
  * The call linearises at the current parameters (with that linearisation's
  * Jacobi scaling), forms and factors the undamped DENSE_SCHUR reduced system,
@@ -441,10 +441,48 @@ typedef struct {
 } ba_covariance_request;
 int ba_covariance(ba_ctx* ctx, const ba_covariance_request* req);
 
+/* ba_covariance for any pair of parameter blocks, and the leverages of
+ * observations, from the same single factorisation and inverse.  `base` is
+ * served exactly as by ba_covariance (bitwise the same output).  With
+ * Sigma = (J^T J)^-1 over the variable blocks, T_p = Hpp_p^-1 Hpc_p:
+ *   cam_pt_cov    Cov(cam i, point p) = -(Sigma_cc T_p^T)[i], 6x3,
+ *   pt_pt_cov     Cov(p, q) = T_p Sigma_cc T_q^T + delta_pq Hpp_p^-1, 3x3; for
+ *                 p == q bitwise the marginal of `base`; Cov(p, q)^T and
+ *                 Cov(q, p) are bitwise equal,
+ *   leverage      h_o = J_o Sigma J_o^T, the 2x2 diagonal block of the hat
+ *                 matrix J Sigma J^T of observation o (J_o = [Jc | Jp], 2x9;
+ *                 a constant block contributes nothing; every duplicate of an
+ *                 observation has its own h_o).  h_o is symmetric; with J of
+ *                 full column rank the traces of all h_o sum to the number of
+ *                 variable parameters.
+ * Any block with a constant camera or constant point is all zeros; so is the
+ * leverage of an observation whose two blocks are both constant.
+ * Contract and errors are ba_covariance's: it linearises at the current
+ * parameters, factors and inverts once whatever is requested, leaves the
+ * parameters and the context as they were (a later ba_solve, ba_covariance or
+ * ba_debug_blocks is bit for bit what it would have been), gives bitwise
+ * equal output on a second call, and blocks until the results are on the
+ * host.  BA_ERR_INVALID_ARGUMENT also for an observation index out of range;
+ * BA_ERR_SINGULAR also for a non-finite requested entry of the new outputs. */
+typedef struct {
+  ba_covariance_request base;      /* camera pairs and point marginals, exactly as ba_covariance */
+  int32_t n_cam_pt, n_pt_pairs;
+  const int32_t* cam_pt;           /* [2*n_cam_pt] (camera, point), caller indices */
+  double*        cam_pt_cov;       /* [18*n_cam_pt] row-major 6x3 Cov(cam, pt) */
+  const int32_t* pt_pairs;         /* [2*n_pt_pairs] (p, q), any order, p == q allowed */
+  double*        pt_pt_cov;        /* [9*n_pt_pairs] row-major 3x3 Cov(p, q) */
+  int32_t n_lev, reserved;
+  const int32_t* lev_obs;          /* [n_lev] caller observation indices; NULL with
+                                      n_lev == n_obs: every observation in caller order */
+  double*        leverage;         /* [4*n_lev] row-major 2x2 */
+} ba_covariance_request_ex;
+int ba_covariance_ex(ba_ctx* ctx, const ba_covariance_request_ex* req);
+
 /* Device time (ms, HIP events) of the phases of the last successful
- * ba_covariance: [0] linearisation + reduced system, [1] factorisation (the
+ * ba_covariance or ba_covariance_ex: [0] linearisation + reduced system (and
+ * the J records when leverages are requested), [1] factorisation (the
  * launches of a DENSE_SCHUR step's), [2] inverse of the factor and
- * Sigma = L^-T L^-1, [3] block gathers and the copies to the host.  Copies
+ * Sigma = L^-T L^-1, [3] all block gathers and the copies to the host.  Copies
  * min(n, 4) values, returns 4 (0 before the first call).  Diagnostic. */
 int ba_covariance_times(ba_ctx* ctx, double* ms, int n);
 

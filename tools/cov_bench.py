@@ -15,6 +15,11 @@ Reported, one JSON record:
             factorisation (the launches of a DENSE_SCHUR step), inverse,
             gathers; the median of --reps calls after one warm-up.  Also the
             same call with the camera blocks only.
+  feature_ex  ba_covariance_ex legs, each with its wall time and the four phase
+            times: the diagonal camera blocks only; the leverages of all
+            observations only; every observed point's cross block with its
+            first observing camera only; all of these and the point marginals
+            in one call.  A leg minus the cameras-only leg isolates its pass.
   host      the route without it, cameras only (it cannot produce the points):
             ba_debug_blocks at an infinite radius (the undamped S to the
             host), then LAPACK potrf + potri on the host's threads, then the
@@ -77,6 +82,38 @@ def main():
                           "device_ms_linearise_and_reduced_system": float(ph[0]), "device_ms_factorisation": float(ph[1]),
                           "device_ms_inverse": float(ph[2]), "device_ms_gathers": float(ph[3]),
                           "wall_ms_cameras_only": median(wall_c)}
+        # ba_covariance_ex legs; the new pass alone is a leg minus "cameras_only"
+        first = np.full(p.n_pts, -1, np.int64)
+        u, i = np.unique(p.obs_pt, return_index=True)        # each point's first observing camera
+        first[u] = p.obs_cam[i]
+        cam_pt = np.stack([first[points], points], 1).astype(np.int32)
+        diag = np.stack([np.arange(p.n_cams)] * 2, 1).astype(np.int32)
+        legs = {"cameras_only": dict(cam_pairs=diag),
+                "all_leverages": dict(leverage_obs="all"),
+                "cross_block_per_point": dict(cam_pt=cam_pt),
+                "cameras_points_cross_leverages": dict(cam_pairs=diag, points=points, cam_pt=cam_pt,
+                                                       leverage_obs="all")}
+        rec["feature_ex"] = {"leverages_requested": p.n_obs, "cross_blocks_requested": int(cam_pt.shape[0])}
+        for leg, kw in legs.items():
+            s.covariance_ex(**kw)                            # warm-up (the J records' first allocation)
+            wall, phases = [], []
+            for _ in range(a.reps):
+                t = time.perf_counter()
+                out = s.covariance_ex(**kw)
+                wall.append((time.perf_counter() - t) * 1e3)
+                phases.append(s.covariance_times())
+            ph = np.median(np.stack(phases), axis=0)
+            rec["feature_ex"][leg] = {"wall_ms": median(wall), "device_ms": float(ph.sum()),
+                                      "device_ms_linearise_and_reduced_system": float(ph[0]),
+                                      "device_ms_factorisation": float(ph[1]), "device_ms_inverse": float(ph[2]),
+                                      "device_ms_gathers": float(ph[3])}
+            if "leverages" in leg:   # (their traces sum to n_variable_parameters)
+                lev = out["leverage"]
+                rec["feature_ex"][leg]["trace_sum"] = float(np.einsum("oii->", lev))
+                rec["feature_ex"][leg]["max_leverage_entry"] = float(lev.max())
+        var_c = (p.cam_fixed == 0) & (np.bincount(p.obs_cam, minlength=p.n_cams) > 0)
+        pt_fixed = np.zeros(p.n_pts, bool) if p.pt_fixed is None else p.pt_fixed != 0
+        rec["n_variable_parameters"] = 6 * int(var_c.sum()) + 3 * int((seen & ~pt_fixed).sum())
         # host route: S at an infinite radius to the host, potrf + potri there
         n = C.c_int(0)
         s._check(s.lib.ba_debug_blocks(s.h, float("inf"), None, None, None, None, None, None, C.byref(n)), "sizing")
