@@ -114,6 +114,17 @@ class ba_covariance_request_ex(C.Structure):
     ]
 
 
+class ba_cov_iter_options(C.Structure):
+    _fields_ = [("preconditioner_type", C.c_int32), ("max_iterations", C.c_int32), ("tolerance", C.c_double)]
+
+
+class ba_cov_iter_info(C.Structure):
+    _fields_ = [
+        ("n_columns", C.c_int32), ("n_converged", C.c_int32), ("max_iterations_used", C.c_int32),
+        ("reserved", C.c_int32), ("max_residual", C.c_double), ("ms", C.c_double * 4),
+    ]
+
+
 # int (*)(void* user, double* values, int64_t n, int op) of ba_comm_init_host
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int)
 
@@ -153,6 +164,10 @@ SIGNATURES = [
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
     ("ba_covariance_ex", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request_ex)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ba_covariance_iterative_defaults", None, [C.POINTER(ba_cov_iter_options)]),
+    ("ba_covariance_iterative", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request),
+                                          C.POINTER(ba_cov_iter_options), C.POINTER(ba_cov_iter_info)]),
+    ("ba_covariance_iterative_bench", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("ba_synchronize", C.c_int, [C.c_void_p]),
     ("ba_bench_iterations", C.c_int, [C.c_void_p, C.POINTER(ba_options), C.c_int, C.c_double,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -31,6 +31,7 @@
 
 #include "../../include/ba_hip.h"
 #include "ba_device.h"
+#include "ba_cov_pcg.h"
 #include "ba_kernels.h"
 
 using namespace bahip;
@@ -140,6 +141,10 @@ struct ba_ctx {
   size_t pcg_ndup = 0;     // ITERATIVE_SCHUR duplicate (camera, point) pairs (ensure_pcg)
   double* tobs_buf = nullptr;   // [no][6] ITERATIVE_SCHUR per-observation products (allocated on first use)
   int max_no = 0;               // largest observation count over the ranks (collective matvec-path choice)
+  // ba_covariance_iterative: the multi-column CG's scratch (allocated on first
+  // use, grown on demand, freed with the problem) and its capacity in columns
+  bahip::McgBufs mcg{};
+  int mcg_cols = 0;
 
   // solver state
   std::vector<ba_iteration> log;
@@ -175,6 +180,8 @@ struct ba_ctx {
     allocs.clear();
     have_problem = have_dense = have_pcg = false;
     tobs_buf = nullptr;
+    mcg = bahip::McgBufs{};
+    mcg_cols = 0;
     scale_valid = false;
     log.clear();
   }
@@ -1029,11 +1036,21 @@ int reduced_solve_pcg(ba_ctx* ctx, double radius, const ba_options& o) {
 // batches of CG iterations) / read back.  Returns the linear-solver iterations.
 // the per-observation Schur blocks of a step: fp32 or fp64, compact records,
 // camera-major copies
-void step_w_storage(ba_ctx* ctx, const ba_options& o) {
+// plain_w: the plain 18-value fp64 records whatever the options and the
+// environment would select (ba_covariance_iterative reads them in its own
+// passes; every later step decides again)
+void step_w_storage(ba_ctx* ctx, const ba_options& o, bool plain_w = false) {
   DevWork& W = ctx->W;
-  W.w32 = o.precision == BA_MIXED_FP32;
+  W.w32 = !plain_w && o.precision == BA_MIXED_FP32;
   if (W.w32 && !W.Wf) W.Wf = ctx->dalloc<float>(18 * (size_t)ctx->no);
   if (!W.w32 && !W.W) W.W = ctx->dalloc<double>(18 * (size_t)ctx->no);
+  if (plain_w) {
+    W.wcompact = W.pcgc = W.pcgjf = W.pacc = false;
+    W.jdiag = W.jrfree;   // (the diagonal blocks J-free, as every ITERATIVE_SCHUR step forms them)
+    if (W.jdiag && !W.prec) W.prec = ctx->dalloc<double>(16 * (size_t)std::max(ctx->np, 1));
+    W.mcc_cam = ctx->rank == 0;
+    return;
+  }
   {
     // compact W records (ba_kernels.hip k_obs_w_rc<double, true>): the
     // J-free fp64 DENSE_SCHUR iteration with the fused point step (the only
@@ -1350,6 +1367,26 @@ void get_params(ba_ctx* ctx, double* cams, double* pts) {
   if (pts && ctx->np) HIP_OK(hipMemcpy(pts, ctx->W.pts, 3 * sizeof(double) * ctx->np, hipMemcpyDeviceToHost));
 }
 
+// compact index of a requested camera (-1: constant) and the check of a
+// requested point, shared by the covariance entry points (fn: the entry
+// point's name for messages)
+int cov_cam_index(const ba_ctx* ctx, const std::string& fn, int c) {
+  if (c < 0 || c >= ctx->nc)
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": camera index " + std::to_string(c) + " out of range"};
+  const int v = ctx->h_vc[c];
+  if (v < 0 && !ctx->cam_fixed_h[c])
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": camera " + std::to_string(c) +
+                                               " is variable but has no observation"};
+  return v;
+}
+void cov_check_point(const ba_ctx* ctx, const std::string& fn, int p) {
+  if (p < 0 || p >= ctx->np)
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": point index " + std::to_string(p) + " out of range"};
+  if (!ctx->h_pt_var[p] && !ctx->pt_fixed_h[p])
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": point " + std::to_string(p) +
+                                               " is variable but has no observation"};
+}
+
 // ---------------------------------------------------------------------------
 // ceres::Covariance (defaults) for any pair of parameter blocks, and the
 // leverages J_o Sigma J_o^T of observations (ba_covariance, ba_covariance_ex;
@@ -1369,23 +1406,8 @@ void covariance(ba_ctx* ctx, const ba_covariance_request_ex* rx, const std::stri
       (npp > 0 && (!rx->pt_pairs || !rx->pt_pt_cov)) || (nlev > 0 && !rx->leverage) ||
       (nlev > 0 && !rx->lev_obs && nlev != ctx->no))
     throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": bad sizes or missing array"};
-  // compact index of a requested camera (-1: constant), point checks
-  auto cam_index = [&](int c) {
-    if (c < 0 || c >= ctx->nc)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": camera index " + std::to_string(c) + " out of range"};
-    const int v = ctx->h_vc[c];
-    if (v < 0 && !ctx->cam_fixed_h[c])
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": camera " + std::to_string(c) +
-                                                 " is variable but has no observation"};
-    return v;
-  };
-  auto check_point = [&](int p) {
-    if (p < 0 || p >= ctx->np)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": point index " + std::to_string(p) + " out of range"};
-    if (!ctx->h_pt_var[p] && !ctx->pt_fixed_h[p])
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": point " + std::to_string(p) +
-                                                 " is variable but has no observation"};
-  };
+  auto cam_index = [&](int c) { return cov_cam_index(ctx, fn, c); };
+  auto check_point = [&](int p) { cov_check_point(ctx, fn, p); };
   std::vector<int2> pairs_h(m), cp_h(ncp);
   for (int q = 0; q < m; ++q) {
     const int v0 = cam_index(req->cam_pairs[2 * q]), v1 = cam_index(req->cam_pairs[2 * q + 1]);
@@ -1557,6 +1579,313 @@ void covariance(ba_ctx* ctx, const ba_covariance_request_ex* rx, const std::stri
     float ms = 0.0f;
     HIP_OK(hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
     ctx->cov_ms[i] = ms;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// ba_covariance_iterative: ba_covariance's request from block columns of
+// S_scaled^-1 solved by multi-column PCG on the implicit reduced camera system
+// (ba_cov_pcg.hip).  Prologue as covariance(): linearisation with its Jacobi
+// scaling, the step's W records (the plain fp64 form), an infinite radius.
+// ---------------------------------------------------------------------------
+void mcg_ensure(ba_ctx* ctx, int B) {
+  const int R = 6 * B;
+  if (ctx->mcg_cols >= R) return;
+  bahip::McgBufs& b = ctx->mcg;
+  for (double* p : {b.X, b.Rv, b.Z, b.Pv, b.Q, b.T, b.Vp, b.part}) ctx->dfree(p);
+  b.X = b.Rv = b.Z = b.Pv = b.Q = b.T = b.Vp = b.part = nullptr;
+  ctx->mcg_cols = 0;
+  const size_t vec = (size_t)std::max(ctx->nvc, 1) * 6 * R;
+  const size_t groups = (size_t)(std::max(ctx->nvc, 1) + bahip::kMcgGroup - 1) / bahip::kMcgGroup;
+  b.X = ctx->dalloc<double>(vec);
+  b.Rv = ctx->dalloc<double>(vec);
+  b.Z = ctx->dalloc<double>(vec);
+  b.Pv = ctx->dalloc<double>(vec);
+  b.Q = ctx->dalloc<double>(vec);
+  b.T = ctx->dalloc<double>(vec * (size_t)std::max(ctx->W.pcg_G, 1));
+  b.Vp = ctx->dalloc<double>((size_t)std::max(ctx->np, 1) * 3 * R);   // (the large one: why B is small)
+  b.part = ctx->dalloc<double>(3 * groups * R);
+  if (!b.st) b.st = ctx->dalloc<double>(bahip::kMcgState);
+  ctx->mcg_cols = R;
+}
+
+void covariance_iterative(ba_ctx* ctx, const ba_covariance_request* req, const ba_cov_iter_options* opt_in,
+                          ba_cov_iter_info* info) {
+  const std::string fn = "ba_covariance_iterative";
+  if (!req) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": request is NULL"};
+  if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, fn + " before ba_set_problem"};
+  if (ctx->has_comm())
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": not available on a context with a communicator"};
+  ba_cov_iter_options co;
+  ba_covariance_iterative_defaults(&co);
+  if (opt_in) co = *opt_in;
+  if (!(co.tolerance > 0.0) || !std::isfinite(co.tolerance))
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": tolerance must be positive and finite"};
+  if (co.max_iterations < 1) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": max_iterations < 1"};
+  if (co.preconditioner_type != BA_JACOBI && co.preconditioner_type != BA_SCHUR_JACOBI)
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": unknown preconditioner"};
+  const int m = req->n_cam_pairs, k = req->n_points;
+  if (m < 0 || k < 0 || (m > 0 && (!req->cam_pairs || !req->cam_cov)) || (k > 0 && (!req->points || !req->pt_cov)))
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": bad sizes or missing array"};
+  std::vector<int2> pairs_h(m);
+  for (int q = 0; q < m; ++q) {
+    const int v0 = cov_cam_index(ctx, fn, req->cam_pairs[2 * q]), v1 = cov_cam_index(ctx, fn, req->cam_pairs[2 * q + 1]);
+    pairs_h[q] = make_int2(v0, v1);
+  }
+  for (int q = 0; q < k; ++q) cov_check_point(ctx, fn, req->points[q]);
+  // column cameras, increasing: column j of a pair with both cameras
+  // variable, every variable observer of a requested variable point
+  std::vector<char> is_col(std::max(ctx->nvc, 1), 0);
+  for (const int2& pr : pairs_h)
+    if (pr.x >= 0 && pr.y >= 0) is_col[pr.y] = 1;
+  for (int q = 0; q < k; ++q) {
+    const int p = req->points[q];
+    if (!ctx->h_pt_var[p]) continue;
+    for (int o = ctx->h_pt_off[p]; o < ctx->h_pt_off[p + 1]; ++o) {
+      const int v = ctx->h_vc[ctx->h_obs_cam[o]];
+      if (v >= 0) is_col[v] = 1;
+    }
+  }
+  std::vector<int> cols;
+  for (int v = 0; v < ctx->nvc; ++v)
+    if (is_col[v]) cols.push_back(v);
+  // the pair requests with a column, ordered by column camera; col_off[c]: the
+  // first of column camera cols[c]
+  std::vector<int> ord, col_off(cols.size() + 1, 0);
+  {
+    std::vector<int> rank(std::max(ctx->nvc, 1), -1);
+    for (size_t c = 0; c < cols.size(); ++c) rank[cols[c]] = (int)c;
+    for (int q = 0; q < m; ++q)
+      if (pairs_h[q].x >= 0 && pairs_h[q].y >= 0) ++col_off[rank[pairs_h[q].y] + 1];
+    for (size_t c = 0; c < cols.size(); ++c) col_off[c + 1] += col_off[c];
+    ord.resize(col_off[cols.size()]);
+    std::vector<int> fill(col_off.begin(), col_off.end() - 1);
+    for (int q = 0; q < m; ++q)
+      if (pairs_h[q].x >= 0 && pairs_h[q].y >= 0) ord[fill[rank[pairs_h[q].y]]++] = q;
+  }
+  // column cameras per pass: BA_COV_PCG_COLS (diagnostics, read per call) forces 1, 2 or 4
+  int B = cols.size() >= 3 ? 4 : (cols.size() == 2 ? 2 : 1);
+  if (const char* be = getenv("BA_COV_PCG_COLS")) {
+    const int f = atoi(be);
+    if (f == 1 || f == 2 || f == 4) B = f;
+  }
+  const int R = 6 * B;
+  HIP_OK(hipSetDevice(ctx->device));
+  ba_options o;
+  ba_default_options(&o);
+  ctx->read_env();
+  const hipStream_t s = ctx->stream;
+  struct Events {
+    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  } ev;
+  for (hipEvent_t& x : ev.e) HIP_OK(hipEventCreate(&x));
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  auto add_ms = [&](int slot, hipEvent_t a, hipEvent_t b) {
+    float t = 0.0f;
+    HIP_OK(hipEventElapsedTime(&t, a, b));
+    ms[slot] += t;
+  };
+  HIP_OK(hipEventRecord(ev.e[0], s));
+  const LinResult L = linearize(ctx, true, o.min_lm_diagonal, o.max_lm_diagonal);
+  if (!L.ok) throw BaError{BA_ERR_SINGULAR, fn + ": the linearisation is not finite"};
+  DevProblem& P = ctx->P;
+  DevWork& W = ctx->W;
+  step_w_storage(ctx, o, true);
+  ensure_pcg(ctx);
+  const double radius = std::numeric_limits<double>::infinity();   // every D = sqrt(diag / radius) is exactly 0
+  const bool sj = co.preconditioner_type == BA_SCHUR_JACOBI;
+  launch_point_elim(P, W, radius, s, nullptr);
+  launch_cam_schur_diag(P, W, s, W.Sd);
+  if (sj && ctx->pcg_ndup > 0) launch_pcg_dup(P, W, s);
+  launch_reduce(W, bit(SL_ELIM_BAD), 0, s);
+  ctx->read_scalars();
+  if (ctx->h_scal[SL_ELIM_BAD] != 0.0)
+    throw BaError{BA_ERR_SINGULAR, fn + ": " + std::to_string((long long)ctx->h_scal[SL_ELIM_BAD]) +
+                                       " point block(s) not positive definite"};
+  mcg_ensure(ctx, B);
+  const bahip::McgBufs& mb = ctx->mcg;
+  std::vector<double> hst(bahip::kMcgState, 0.0);
+  if (ctx->nvc > 0) {
+    HIP_OK(hipMemsetAsync(mb.st, 0, sizeof(double) * bahip::kMcgState, s));
+    bahip::launch_mcg_blocks(P, W, sj, mb.st, s);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(hst.data(), mb.st, sizeof(double) * bahip::kMcgState, hipMemcpyDeviceToHost, s));
+  }
+  HIP_OK(hipEventRecord(ev.e[1], s));
+  HIP_OK(hipStreamSynchronize(s));
+  add_ms(0, ev.e[0], ev.e[1]);
+  if (hst[bahip::MS_BADBLK] != 0.0)
+    throw BaError{BA_ERR_SINGULAR, fn + ": a preconditioner block is not positive definite"};
+  // request and result staging (freed on every exit)
+  enum { D_PAIRS, D_ORD, D_CAM, D_PTS, D_ACC, D_PT, D_N };
+  struct Dev {
+    void* p[D_N] = {};
+    ~Dev() { for (void* x : p) if (x) (void)hipFree(x); }
+  } d;
+  auto stage = [&](int slot, const void* src, size_t bytes) {
+    HIP_OK(hipMalloc(&d.p[slot], std::max<size_t>(bytes, 8)));
+    if (src && bytes) HIP_OK(hipMemcpyAsync(d.p[slot], src, bytes, hipMemcpyHostToDevice, s));
+    else if (bytes) HIP_OK(hipMemsetAsync(d.p[slot], 0, bytes, s));   // (zeros: the blocks of constant cameras)
+  };
+  if (m > 0) {
+    stage(D_PAIRS, pairs_h.data(), sizeof(int2) * (size_t)m);
+    stage(D_ORD, ord.data(), sizeof(int) * ord.size());
+    stage(D_CAM, nullptr, sizeof(double) * 36 * (size_t)m);
+  }
+  if (k > 0) {
+    stage(D_PTS, req->points, sizeof(int) * (size_t)k);
+    stage(D_ACC, nullptr, sizeof(double) * 9 * (size_t)k);
+    stage(D_PT, nullptr, sizeof(double) * 9 * (size_t)k);
+  }
+  int n_conv = 0, iters_used = 0;
+  double max_res = 0.0;
+  bool broke = false;
+  const int ng = (std::max(ctx->nvc, 1) + bahip::kMcgGroup - 1) / bahip::kMcgGroup;
+  std::vector<double> hpart((size_t)ng * R);
+  for (size_t c0 = 0; c0 < cols.size(); c0 += (size_t)B) {
+    const int nb = (int)std::min<size_t>((size_t)B, cols.size() - c0);
+    bahip::McgPass ps;
+    for (int b = 0; b < bahip::kMcgMaxB; ++b) ps.cc[b] = b < nb ? cols[c0 + b] : -1;
+    HIP_OK(hipEventRecord(ev.e[1], s));
+    bahip::launch_mcg_init(P, W, mb, B, ps, co.tolerance, s);
+    // iterations in growing batches; the state record between them (the
+    // kernels of a pass whose columns are all done return at once)
+    int it = 0, batch = 4;
+    for (;;) {
+      for (int j = 0; j < batch && it < co.max_iterations; ++j) {
+        ++it;
+        bahip::launch_mcg_matvec(P, W, mb, B, mb.Pv, false, s);
+        if (it % 10 == 0) {   // the residual reset of the single-vector CG: r = e - S x
+          bahip::launch_mcg_update(P, W, mb, B, ps, 1, it, co.tolerance, co.max_iterations, s);
+          bahip::launch_mcg_matvec(P, W, mb, B, mb.X, false, s);
+          bahip::launch_mcg_update(P, W, mb, B, ps, 2, it, co.tolerance, co.max_iterations, s);
+        } else {
+          bahip::launch_mcg_update(P, W, mb, B, ps, 0, it, co.tolerance, co.max_iterations, s);
+        }
+      }
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(hst.data(), mb.st, sizeof(double) * bahip::kMcgState, hipMemcpyDeviceToHost, s));
+      HIP_OK(hipStreamSynchronize(s));
+      if (hst[bahip::MS_ALLDONE] != 0.0 || it >= co.max_iterations) break;
+      batch = std::min(2 * batch, 32);
+    }
+    HIP_OK(hipEventRecord(ev.e[2], s));
+    // the true residual of the final X by one more matvec; its point pass
+    // leaves V_p of every point for the point gathers
+    bahip::launch_mcg_matvec(P, W, mb, B, mb.X, true, s);
+    bahip::launch_mcg_update(P, W, mb, B, ps, 3, it, co.tolerance, co.max_iterations, s);
+    HIP_OK(hipMemcpyAsync(hpart.data(), mb.part + 2 * (size_t)ng * R, sizeof(double) * (size_t)ng * R,
+                          hipMemcpyDeviceToHost, s));
+    bahip::launch_mcg_gather_cam(P, W, mb, B, ps, static_cast<const int2*>(d.p[D_PAIRS]),
+                                 static_cast<const int*>(d.p[D_ORD]), col_off[c0], col_off[c0 + nb],
+                                 static_cast<double*>(d.p[D_CAM]), s);
+    bahip::launch_mcg_gather_pt(P, W, mb, B, ps, static_cast<const int*>(d.p[D_PTS]), k,
+                                static_cast<double*>(d.p[D_ACC]), s);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(ev.e[3], s));
+    HIP_OK(hipStreamSynchronize(s));
+    add_ms(1, ev.e[1], ev.e[2]);
+    add_ms(2, ev.e[2], ev.e[3]);
+    for (int r = 0; r < 6 * nb; ++r) {
+      if (hst[bahip::mcg_slot(bahip::MC_BAD, r)] != 0.0) broke = true;
+      if (hst[bahip::mcg_slot(bahip::MC_CONV, r)] != 0.0) ++n_conv;
+      iters_used = std::max(iters_used, (int)hst[bahip::mcg_slot(bahip::MC_ITERS, r)]);
+      double rr = 0.0;
+      for (int g = 0; g < ng; ++g) rr += hpart[(size_t)g * R + r];
+      const double res = std::sqrt(rr);
+      max_res = std::isfinite(res) ? std::max(max_res, res) : std::numeric_limits<double>::infinity();
+    }
+    if (broke) break;
+  }
+  if (broke)
+    throw BaError{BA_ERR_SINGULAR, fn + ": the conjugate gradients broke down (the reduced camera system or its "
+                                        "preconditioner is not positive definite)"};
+  HIP_OK(hipEventRecord(ev.e[3], s));
+  bahip::launch_mcg_pt_finish(P, W, static_cast<const int*>(d.p[D_PTS]), k, static_cast<const double*>(d.p[D_ACC]),
+                              static_cast<double*>(d.p[D_PT]), s);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(ev.e[2], s));
+  if (m > 0) HIP_OK(hipMemcpyAsync(req->cam_cov, d.p[D_CAM], sizeof(double) * 36 * (size_t)m, hipMemcpyDeviceToHost, s));
+  if (k > 0) HIP_OK(hipMemcpyAsync(req->pt_cov, d.p[D_PT], sizeof(double) * 9 * (size_t)k, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipEventRecord(ev.e[4], s));
+  HIP_OK(hipStreamSynchronize(s));
+  add_ms(2, ev.e[3], ev.e[2]);
+  add_ms(3, ev.e[2], ev.e[4]);
+  for (size_t i = 0; i < 36 * (size_t)m; ++i)
+    if (!std::isfinite(req->cam_cov[i]))
+      throw BaError{BA_ERR_SINGULAR, fn + ": camera block " + std::to_string(i / 36) + " is not finite"};
+  for (size_t i = 0; i < 9 * (size_t)k; ++i)
+    if (!std::isfinite(req->pt_cov[i]))
+      throw BaError{BA_ERR_SINGULAR, fn + ": the block of point " + std::to_string(req->points[i / 9]) +
+                                         " is not finite"};
+  if (info) {
+    info->n_columns = 6 * (int)cols.size();
+    info->n_converged = n_conv;
+    info->max_iterations_used = iters_used;
+    info->reserved = 0;
+    info->max_residual = max_res;
+    for (int i = 0; i < 4; ++i) info->ms[i] = ms[i];
+  }
+}
+
+// ba_covariance_iterative_bench: matvec timings on the iterative covariance's
+// prologue state (cols = 0: launch_pcg_matvec on the same plain W records)
+void covariance_iterative_bench(ba_ctx* ctx, int cols, int reps, int warmup, double* ms) {
+  const std::string fn = "ba_covariance_iterative_bench";
+  if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, fn + " before ba_set_problem"};
+  if (ctx->has_comm())
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": not available on a context with a communicator"};
+  if ((cols != 0 && cols != 1 && cols != 2 && cols != 4) || reps < 1 || warmup < 0 || !ms || ctx->nvc == 0)
+    throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": bad arguments"};
+  HIP_OK(hipSetDevice(ctx->device));
+  ba_options o;
+  ba_default_options(&o);
+  ctx->read_env();
+  const hipStream_t s = ctx->stream;
+  const LinResult L = linearize(ctx, true, o.min_lm_diagonal, o.max_lm_diagonal);
+  if (!L.ok) throw BaError{BA_ERR_SINGULAR, fn + ": the linearisation is not finite"};
+  DevProblem& P = ctx->P;
+  DevWork& W = ctx->W;
+  step_w_storage(ctx, o, true);
+  ensure_pcg(ctx);
+  launch_point_elim(P, W, std::numeric_limits<double>::infinity(), s, nullptr);
+  launch_cam_schur_diag(P, W, s, W.Sd);
+  launch_reduce(W, bit(SL_ELIM_BAD), 0, s);
+  const int B = std::max(cols, 1);
+  mcg_ensure(ctx, B);
+  const bahip::McgBufs& mb = ctx->mcg;
+  HIP_OK(hipMemsetAsync(mb.st, 0, sizeof(double) * bahip::kMcgState, s));
+  bahip::launch_mcg_blocks(P, W, true, mb.st, s);
+  bahip::McgPass ps;
+  for (int b = 0; b < bahip::kMcgMaxB; ++b) ps.cc[b] = b < B ? std::min(b, ctx->nvc - 1) : -1;
+  bahip::launch_mcg_init(P, W, mb, B, ps, 1e-300, s);   // (p = M e: a multi-vector to multiply)
+  // the single-vector form reads its state record's PS_DONE: as a step's setup leaves it
+  const bool had_tobs = W.tobs != nullptr;
+  if (cols == 0) {
+    W.tobs = nullptr;   // (the W-gathering camera pass: the same records as the multi-column form)
+    HIP_OK(hipMemsetAsync(W.scal + kNumSlots, 0, sizeof(double) * kPcgState, s));
+    HIP_OK(hipMemcpyAsync(W.pp, mb.Pv, sizeof(double) * (size_t)ctx->n, hipMemcpyDeviceToDevice, s));
+  }
+  std::vector<hipEvent_t> ev(2 * (size_t)reps, nullptr);
+  struct Guard {
+    std::vector<hipEvent_t>& e;
+    ~Guard() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  } guard{ev};
+  for (hipEvent_t& x : ev) HIP_OK(hipEventCreate(&x));
+  for (int i = 0; i < warmup + reps; ++i) {
+    if (i >= warmup) HIP_OK(hipEventRecord(ev[2 * (size_t)(i - warmup)], s));
+    if (cols == 0) launch_pcg_matvec(P, W, W.pp, s);
+    else bahip::launch_mcg_matvec(P, W, mb, B, mb.Pv, true, s);
+    if (i >= warmup) HIP_OK(hipEventRecord(ev[2 * (size_t)(i - warmup) + 1], s));
+  }
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(s));
+  if (cols == 0 && had_tobs) W.tobs = ctx->tobs_buf;
+  for (int i = 0; i < reps; ++i) {
+    float t = 0.0f;
+    HIP_OK(hipEventElapsedTime(&t, ev[2 * (size_t)i], ev[2 * (size_t)i + 1]));
+    ms[i] = t;
   }
 }
 
@@ -2305,6 +2634,24 @@ int ba_covariance(ba_ctx* ctx, const ba_covariance_request* req) {
     rx.base = *req;
     covariance(ctx, &rx, "ba_covariance");
   });
+}
+
+void ba_covariance_iterative_defaults(ba_cov_iter_options* opt) {
+  if (!opt) return;
+  opt->preconditioner_type = BA_SCHUR_JACOBI;
+  opt->max_iterations = 500;
+  opt->tolerance = 1e-10;
+}
+
+int ba_covariance_iterative(ba_ctx* ctx, const ba_covariance_request* req, const ba_cov_iter_options* opt,
+                            ba_cov_iter_info* info) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { covariance_iterative(ctx, req, opt, info); });
+}
+
+int ba_covariance_iterative_bench(ba_ctx* ctx, int cols, int reps, int warmup, double* ms) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { covariance_iterative_bench(ctx, cols, reps, warmup, ms); });
 }
 
 int ba_covariance_times(ba_ctx* ctx, double* ms, int n) {

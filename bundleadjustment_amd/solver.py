@@ -307,6 +307,51 @@ class Solver:
         self._check(self.lib.ba_covariance_ex(self.h, C.byref(req)), "ba_covariance_ex")
         return out
 
+    def covariance_iterative(self, cam_pairs=None, points=None, *, preconditioner: str = "schur_jacobi",
+                             max_iterations: int = 500, tolerance: float = 1e-10
+                             ) -> tuple[np.ndarray, np.ndarray, dict]:
+        """covariance()'s request without the dense factor
+        (ba_covariance_iterative): the blocks come from block columns of the
+        inverse reduced camera system, each column solved by preconditioned
+        conjugate gradients on the implicit system until |r|_2 <= tolerance
+        or max_iterations.  Serves problems too large for DENSE_SCHUR.
+        cam_pairs / points as in covariance(); preconditioner "jacobi" or
+        "schur_jacobi".  Returns (cam_cov [m, 6, 6], pt_cov [k, 3, 3], info)
+        with info: n_columns, n_converged, max_iterations_used, max_residual
+        (the largest true |e - S x|_2 over the columns) and ms (device time
+        of setup, CG, residual check + gathers, copies).  A column that does
+        not converge is reported in info, not raised."""
+        kinds = {"jacobi": 0, "schur_jacobi": 1}
+        if preconditioner not in kinds:
+            raise ValueError(f"covariance_iterative: preconditioner = {preconditioner!r}")
+        if cam_pairs is None:
+            i = np.arange(self.problem.n_cams, dtype=np.int32)
+            cam_pairs = np.stack([i, i], axis=1)
+        cp = np.ascontiguousarray(cam_pairs, dtype=np.int32).reshape(-1, 2)
+        pt = np.ascontiguousarray(points if points is not None else [], dtype=np.int32).reshape(-1)
+        cam_cov = np.empty((cp.shape[0], 6, 6))
+        pt_cov = np.empty((pt.size, 3, 3))
+        req = N.ba_covariance_request(n_cam_pairs=cp.shape[0], n_points=pt.size, cam_pairs=_ptr(cp),
+                                      cam_cov=_ptr(cam_cov), points=_ptr(pt), pt_cov=_ptr(pt_cov))
+        opt = N.ba_cov_iter_options(preconditioner_type=kinds[preconditioner], max_iterations=int(max_iterations),
+                                    tolerance=float(tolerance))
+        info = N.ba_cov_iter_info()
+        self._check(self.lib.ba_covariance_iterative(self.h, C.byref(req), C.byref(opt), C.byref(info)),
+                    "ba_covariance_iterative")
+        return cam_cov, pt_cov, {"n_columns": info.n_columns, "n_converged": info.n_converged,
+                                 "max_iterations_used": info.max_iterations_used,
+                                 "max_residual": info.max_residual, "ms": [float(x) for x in info.ms]}
+
+    def covariance_iterative_bench(self, cols: int, reps: int = 20, warmup: int = 3) -> np.ndarray:
+        """Device time (ms) of `reps` implicit matvecs on covariance_iterative's
+        W records: cols = 0 the single-vector matvec of ITERATIVE_SCHUR, cols =
+        1, 2, 4 the multi-column one with that many column cameras
+        (ba_covariance_iterative_bench).  Diagnostic."""
+        ms = np.empty(int(reps))
+        self._check(self.lib.ba_covariance_iterative_bench(self.h, int(cols), int(reps), int(warmup), _ptr(ms)),
+                    "ba_covariance_iterative_bench")
+        return ms
+
     def covariance_times(self) -> np.ndarray:
         """Device time (ms) of the phases of the last covariance() / covariance_ex() call:
         linearisation + reduced system, factorisation, inverse, gathers."""

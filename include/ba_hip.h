@@ -486,6 +486,66 @@ int ba_covariance_ex(ba_ctx* ctx, const ba_covariance_request_ex* req);
  * min(n, 4) values, returns 4 (0 before the first call).  Diagnostic. */
 int ba_covariance_times(ba_ctx* ctx, double* ms, int n);
 
+/* ba_covariance's request (camera pairs and point marginals) without the
+ * dense factor: the requested blocks come from a few block columns of
+ * S_scaled^-1, each solved by preconditioned conjugate gradients on the
+ * implicit reduced camera system (the ITERATIVE_SCHUR matvec, several
+ * right-hand sides per pass over the per-observation blocks).  Neither S nor
+ * its factor is formed, so the call serves problems DENSE_SCHUR refuses.
+ * Cross blocks and leverages stay with ba_covariance_ex.
+ *
+ * Semantics are ba_covariance's: (J^T J)^-1 over the variable blocks at the
+ * current parameters, unscaled, undamped; blocks of constant cameras or
+ * points are exact zeros; the gauge is the caller's to fix.  For a pair
+ * (i, j) of variable cameras the block is read from the six columns of
+ * camera j; a variable point needs the columns of all its variable observers.
+ * Every column e is solved from x = 0 until |r|_2 <= tolerance (|e|_2 = 1)
+ * or max_iterations, in the Jacobi-scaled system.  A block's bits depend only
+ * on the problem, the parameters and the options, not on what else is
+ * requested; two calls give bitwise equal output.  Cov(i, j) and Cov(j, i)^T
+ * come from different columns: they agree to the tolerance, not bitwise.
+ *
+ * A column that does not converge is not an error: the call returns BA_OK,
+ * the outputs are formed from the last iterate and `info` reports it.
+ * Errors (the context stays usable after each; a later ba_solve,
+ * ba_covariance or ba_debug_blocks is bit for bit what it would have been):
+ *   BA_ERR_NO_PROBLEM        before ba_set_problem,
+ *   BA_ERR_INVALID_ARGUMENT  ba_covariance's, and: a tolerance that is not
+ *                            positive and finite, max_iterations < 1, an
+ *                            unknown preconditioner; a context with a
+ *                            communicator,
+ *   BA_ERR_SINGULAR          a point block or a preconditioner block is not
+ *                            positive definite, the CG broke down (p^T S p
+ *                            <= 0 or not finite), or a requested entry is not
+ *                            finite. */
+typedef struct {
+  int32_t preconditioner_type;   /* BA_JACOBI | BA_SCHUR_JACOBI (default BA_SCHUR_JACOBI) */
+  int32_t max_iterations;        /* per column, default 500 */
+  double  tolerance;             /* tau: a column stops when |r|_2 <= tau (|e|_2 = 1), default 1e-10 */
+} ba_cov_iter_options;
+
+typedef struct {
+  int32_t n_columns;             /* 6 x distinct column cameras solved */
+  int32_t n_converged;           /* columns that met tau within max_iterations */
+  int32_t max_iterations_used, reserved;
+  double  max_residual;          /* max over columns of the TRUE |e - S x|_2, recomputed by one matvec */
+  double  ms[4];                 /* linearise+W+preconditioner | CG | residual check + gathers | copies */
+} ba_cov_iter_info;
+
+void ba_covariance_iterative_defaults(ba_cov_iter_options* opt);
+int  ba_covariance_iterative(ba_ctx* ctx, const ba_covariance_request* req,
+                             const ba_cov_iter_options* opt /* NULL = defaults */,
+                             ba_cov_iter_info* info /* may be NULL */);
+
+/* Diagnostic: device time (ms, HIP events, one pair per launch pair) of `reps`
+ * implicit matvecs after `warmup` untimed ones, on the current problem with
+ * ba_covariance_iterative's prologue and W records.  cols = 0: the
+ * single-vector matvec of ITERATIVE_SCHUR on the same records; cols = 1, 2, 4:
+ * the multi-column matvec with that many column cameras (6 cols columns).
+ * ms[reps].  Single rank only; the context stays usable as after
+ * ba_covariance_iterative. */
+int ba_covariance_iterative_bench(ba_ctx* ctx, int cols, int reps, int warmup, double* ms);
+
 /* Blocks until all device work of the context is done. */
 int ba_synchronize(ba_ctx* ctx);
 

@@ -3,6 +3,7 @@
 
   python tools/cov_bench.py --config c3      --out profiles/cov_bench_c3.json
   python tools/cov_bench.py --config c4shard --out profiles/cov_bench_c4shard.json
+  python tools/cov_bench.py --iterative --config c3 --config c4 --out profiles/cov_iter_bench.json
 
 (on the GPU box through tools/gpu_run.sh: step cov:c3 / cov:c4shard, which
 gives the run its time limit).  The problem is the BASELINE config with
@@ -27,6 +28,19 @@ Reported, one JSON record:
             result (a user of the route would have to recompute them from J).
   agreement the largest |feature - host| / sqrt(v_i v_j) over the diagonal
             camera blocks.
+
+--iterative times ba_covariance_iterative instead, per config (medians of
+--reps runs after --warmup, HIP events unless noted; --request-reps /
+--request-warmup set the runs of the request legs, whose calls take seconds
+at C4, and --no-forced-b drops the legs with B forced):
+  matvec    one implicit matvec: the single-vector launch_pcg_matvec of
+            ITERATIVE_SCHUR ("single") against the multi-column one with B = 1,
+            2, 4 column cameras (6, 12, 24 columns) on the same W records
+  one_column_camera   one diagonal camera block end to end (one column camera,
+            B = 1): wall time and the call's four phase times
+  request   16 camera blocks + 64 points: ba_covariance_iterative (default B,
+            and B forced to 1, 2, 4) against ba_covariance for the same request
+            (wall time), and their largest disagreement
 """
 import argparse
 import ctypes as C
@@ -44,19 +58,97 @@ sys.path.insert(0, str(ROOT))
 from bundleadjustment_amd import Solver, make_config   # noqa: E402
 from bundleadjustment_amd.problem import fix_camera    # noqa: E402
 
-CONFIGS = {"c3": ("c3", 1.0), "c4shard": ("c4", 0.125)}
+CONFIGS = {"c3": ("c3", 1.0), "c4shard": ("c4", 0.125), "c4": ("c4", 1.0)}
 
 
 def median(v):
     return float(np.median(np.asarray(v, float)))
 
 
+def iterative_record(config, reps, warmup, request_reps, request_warmup, forced_b):
+    """The --iterative measurements of one config (a progress line per stage)."""
+    def say(*a):
+        print(f"[{config} {time.strftime('%H:%M:%S')}]", *a, flush=True)
+    name, scale = CONFIGS[config]
+    say("building the problem")
+    p = fix_camera(make_config(name, scale=scale), 1)
+    rec = {"config": config, "n_cams": p.n_cams, "n_pts": p.n_pts, "n_obs": p.n_obs, "reps": reps, "warmup": warmup,
+           "request_reps": request_reps, "request_warmup": request_warmup}
+    rng = np.random.default_rng(1)
+    cams = np.sort(rng.choice(np.arange(2, p.n_cams), size=16, replace=False))
+    pairs = np.stack([cams, cams], 1).astype(np.int32)
+    seen = np.flatnonzero(np.bincount(p.obs_pt, minlength=p.n_pts) > 0)
+    points = np.sort(rng.choice(seen, size=64, replace=False)).astype(np.int32)
+
+    def timed(fn, reps=reps, warmup=warmup):
+        for _ in range(warmup):
+            fn()
+        wall, infos = [], []
+        for _ in range(reps):
+            t = time.perf_counter()
+            out = fn()
+            wall.append((time.perf_counter() - t) * 1e3)
+            infos.append(out[2]["ms"] if len(out) > 2 else None)
+        r = {"wall_ms": median(wall)}
+        if infos[0] is not None:
+            ph = np.median(np.asarray(infos), axis=0)
+            r.update(device_ms_setup=float(ph[0]), device_ms_cg=float(ph[1]),
+                     device_ms_residual_check_and_gathers=float(ph[2]), device_ms_copies=float(ph[3]),
+                     **{k: out[2][k] for k in ("n_columns", "n_converged", "max_iterations_used", "max_residual")})
+        return r, out
+    with Solver(0) as s:
+        s.set_problem(p)
+        say("set_problem done")
+        rec["matvec_ms"] = {}
+        for c in (0, 1, 2, 4):
+            rec["matvec_ms"]["single" if c == 0 else f"B{c}"] = median(s.covariance_iterative_bench(c, reps, warmup))
+            say("matvec", rec["matvec_ms"])
+        rec["one_column_camera"], _ = timed(lambda: s.covariance_iterative(pairs[:1], None))
+        say("one column camera", rec["one_column_camera"])
+        req = {}
+        rr = dict(reps=request_reps, warmup=request_warmup)
+        req["iterative"], it_out = timed(lambda: s.covariance_iterative(pairs, points), **rr)
+        say("request, iterative", req["iterative"])
+        for b in ("1", "2", "4") if forced_b else ():
+            os.environ["BA_COV_PCG_COLS"] = b
+            req[f"iterative_B{b}"], _ = timed(lambda: s.covariance_iterative(pairs, points), **rr)
+            say(f"request, iterative, B = {b}", req[f"iterative_B{b}"])
+        os.environ.pop("BA_COV_PCG_COLS", None)
+        req["dense"], d_out = timed(lambda: s.covariance(pairs, points), **rr)
+        say("request, dense", req["dense"])
+        dc = np.sqrt(np.einsum("kii->ki", d_out[0]))
+        dp = np.sqrt(np.einsum("kii->ki", d_out[1]))
+        req["max_disagreement_cameras"] = float((np.abs(it_out[0] - d_out[0]) / (dc[:, :, None] * dc[:, None, :])).max())
+        req["max_disagreement_points"] = float((np.abs(it_out[1] - d_out[1]) / (dp[:, :, None] * dp[:, None, :])).max())
+        rec["request_16_cameras_64_points"] = req
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", choices=sorted(CONFIGS), required=True)
+    ap.add_argument("--config", choices=sorted(CONFIGS), required=True, action="append")
     ap.add_argument("--out", required=True)
-    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=None)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iterative", action="store_true", help="time ba_covariance_iterative (see the module text)")
+    ap.add_argument("--request-reps", type=int, default=None, help="--iterative: runs of the request legs (default --reps)")
+    ap.add_argument("--request-warmup", type=int, default=None, help="--iterative: their warm-ups (default --warmup)")
+    ap.add_argument("--no-forced-b", action="store_true", help="--iterative: skip the request legs with B forced")
+    ap.add_argument("--append", action="store_true", help="--iterative: extend the record list already in --out")
     a = ap.parse_args()
+    if a.iterative:
+        reps = a.reps or 20
+        out = Path(a.out)
+        recs = json.loads(out.read_text()) if a.append and out.exists() else []
+        recs += [iterative_record(c, reps, a.warmup, a.request_reps or reps,
+                                  a.warmup if a.request_warmup is None else a.request_warmup, not a.no_forced_b)
+                 for c in a.config]
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(json.dumps(recs, indent=1) + "\n")
+        print(json.dumps(recs))
+        return
+    a.config = a.config[-1]
+    a.reps = a.reps or 3
     import scipy.linalg
 
     name, scale = CONFIGS[a.config]
