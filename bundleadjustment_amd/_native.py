@@ -98,6 +98,30 @@ class ba_window_batch(C.Structure):
     ]
 
 
+class ba_tri_batch(C.Structure):
+    _fields_ = [
+        ("n_cams", C.c_int32), ("n_pts", C.c_int32),
+        ("extr", C.c_void_p), ("cam_center", C.c_void_p), ("K", C.c_void_p), ("obs_offset", C.c_void_p),
+        ("obs_cam", C.c_void_p), ("obs_uv", C.c_void_p), ("obs_scale", C.c_void_p), ("pts_init", C.c_void_p),
+        ("huber_a", C.c_double),
+    ]
+
+
+class ba_tri_options(C.Structure):
+    _fields_ = [
+        ("init", C.c_int32), ("refine", C.c_int32), ("min_views", C.c_int32), ("checks", C.c_int32),
+        ("behind_rule", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+# enum ba_tri_status / ba_tri_init / ba_tri_check (include/ba_hip.h)
+TRI_STATUS_NAMES = {0: "OK", 1: "FEW_VIEWS", 2: "DEGENERATE", 3: "BEHIND", 4: "CHI2", 5: "SCALE"}
+TRI_OK, TRI_FEW_VIEWS, TRI_DEGENERATE, TRI_BEHIND, TRI_CHI2, TRI_SCALE = range(6)
+TRI_INIT_DLT, TRI_INIT_GIVEN = 0, 1
+TRI_CHECK_CHEIRALITY, TRI_CHECK_CHI2, TRI_CHECK_SCALE = 1, 2, 4
+TRI_CHECK_ALL = 7
+
+
 class ba_covariance_request(C.Structure):
     _fields_ = [
         ("n_cam_pairs", C.c_int32), ("n_points", C.c_int32), ("cam_pairs", C.c_void_p), ("cam_cov", C.c_void_p),
@@ -161,6 +185,10 @@ SIGNATURES = [
                                         C.c_void_p, C.POINTER(ba_summary)]),
     ("ba_get_window_iteration_log", C.c_int, [C.c_void_p, C.c_int, C.POINTER(ba_iteration), C.c_int]),
     ("ba_window_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ba_triangulate_defaults", None, [C.POINTER(ba_tri_options)]),
+    ("ba_triangulate", C.c_int, [C.c_void_p, C.POINTER(ba_tri_batch), C.POINTER(ba_tri_options),
+                                 C.POINTER(ba_options), C.c_void_p, C.c_void_p, C.POINTER(ba_summary)]),
+    ("ba_triangulate_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
     ("ba_covariance_ex", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request_ex)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

@@ -341,6 +341,29 @@ struct WinArgs {
 size_t window_lds_bytes(int nvc);  // dynamic LDS of a problem with nvc variable observed cameras
 int launch_window_batch(int nprob, const WinArgs& A, const PoseOpts& o, size_t lds_bytes, hipStream_t s);   // hipError_t
 
+// batched triangulation + per-point LM against constant cameras
+// (ba_triangulate.hip): kTriGroup lanes per point, one launch plus the
+// per-camera prologue
+constexpr int kTriGroup = 8;       // lanes per point: a compile-time constant, never chosen from the batch
+constexpr int kTriRec = 64;        // doubles per camera of the scratch: value-only record [0, 48), K-folded table [48, 64)
+struct TriArgs {
+  int n_pts, n_cams;
+  int init_given, refine, min_views, checks, behind_any;
+  double huber_a;
+  // inputs
+  const float* extr; const float* center; const float* K;   // [n_cams][16 | 3 | 9]; center null: scale test off
+  const int* off; const int* obs_cam; const float2* uv;
+  const float* scale;              // [n_obs] or null (all 1)
+  const double* pts_init;          // [n_pts][3] or null (init_given == 0)
+  // scratch
+  double* rec;                     // [n_cams][kTriRec]
+  // outputs
+  double* pts_out;                 // [n_pts][3]
+  double* summ;                    // [n_pts][6]: initial cost, final cost, iterations, successful, unsuccessful, termination
+  uint8_t* status;                 // [n_pts] ba_tri_status
+};
+void launch_triangulate(const TriArgs& A, const PoseOpts& o, hipStream_t s);
+
 int grid_for(int n);
 int pt_group_grid(int np);   // grid of the kPtLanes-lanes-per-point kernels
 

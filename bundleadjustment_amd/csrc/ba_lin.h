@@ -1,7 +1,8 @@
 // ba_lin.h — the per-observation linearisation shared by the general LM
-// kernels (ba_kernels.hip) and the batched small-window solver
-// (ba_window.hip): camera record entries, the value-only projection, the
-// K-folded camera table accessor and lin_obs.  Device code only.
+// kernels (ba_kernels.hip), the batched small-window solver (ba_window.hip)
+// and the batched triangulation (ba_triangulate.hip): camera record entries,
+// the value-only projection, the K-folded camera table accessor and lin_obs.
+// Device code only.
 #pragma once
 #include "ba_device.h"
 #include "ba_kernels.h"

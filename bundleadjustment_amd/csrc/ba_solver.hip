@@ -110,6 +110,12 @@ struct ba_ctx {
   std::vector<int> win_log_n;
   int win_log_cap = 0;
   std::vector<double> win_ms;          // ba_window_times of the last call
+  // ba_triangulate: device staging + camera scratch (grown on demand, reused
+  // across calls), the host copy of its inputs / outputs, the last call's times
+  char* tri_buf = nullptr;
+  size_t tri_cap = 0;
+  std::vector<char> tri_host;
+  std::vector<double> tri_ms;
 
   // host copies of the sorted structure, kept for the lazily built
   // linear-solver structures (Schur pair lists / PCG duplicate pairs)
@@ -2053,6 +2059,7 @@ int ba_destroy(ba_ctx* ctx) {
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
   if (ctx->pose_buf) (void)hipFree(ctx->pose_buf);
   if (ctx->win_buf) (void)hipFree(ctx->win_buf);
+  if (ctx->tri_buf) (void)hipFree(ctx->tri_buf);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -2555,6 +2562,161 @@ int ba_window_times(ba_ctx* ctx, double* ms, int n) {
   if (!ctx) return -BA_ERR_INVALID_ARGUMENT;
   const int m = (int)ctx->win_ms.size();
   for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = ctx->win_ms[i];
+  return m;
+}
+
+// ---------------------------------------------------------------------------
+// ba_triangulate: host side.  Validate everything the kernel indexes with,
+// one staging upload, the prologue + one launch (ba_triangulate.hip), one
+// download.  The context's current problem is not touched.
+// ---------------------------------------------------------------------------
+void ba_triangulate_defaults(ba_tri_options* opt) {
+  if (!opt) return;
+  opt->init = BA_TRI_INIT_DLT;
+  opt->refine = 0;
+  opt->min_views = 2;
+  opt->checks = BA_TRI_CHECK_CHEIRALITY | BA_TRI_CHECK_CHI2 | BA_TRI_CHECK_SCALE;
+  opt->behind_rule = 0;
+  opt->reserved = 0;
+}
+
+int ba_triangulate(ba_ctx* ctx, const ba_tri_batch* b, const ba_tri_options* topt, const ba_options* opt,
+                   double* pts_out, uint8_t* status, ba_summary* summaries) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_triangulate: ";
+    if (!b || b->n_pts < 0 || b->n_cams < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "bad batch"};
+    ba_tri_options t;
+    if (topt) t = *topt; else ba_triangulate_defaults(&t);
+    if (t.init != BA_TRI_INIT_DLT && t.init != BA_TRI_INIT_GIVEN)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "unknown init " + std::to_string(t.init)};
+    if (t.refine != 0 && t.refine != 1) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "unknown refine " + std::to_string(t.refine)};
+    if (t.behind_rule != 0 && t.behind_rule != 1)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "unknown behind_rule " + std::to_string(t.behind_rule)};
+    const int all_checks = BA_TRI_CHECK_CHEIRALITY | BA_TRI_CHECK_CHI2 | BA_TRI_CHECK_SCALE;
+    if (t.checks & ~all_checks) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "unknown checks bits " + std::to_string(t.checks)};
+    if (t.min_views < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "min_views " + std::to_string(t.min_views) + " is negative"};
+    ba_options o;
+    if (opt) o = *opt; else ba_default_options(&o);
+    if (t.refine) {
+      if (o.linear_solver != BA_DENSE_SCHUR) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "linear_solver must be BA_DENSE_SCHUR"};
+      if (o.precision != BA_FP64) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "precision must be BA_FP64"};
+    }
+    const int np = b->n_pts, nc = b->n_cams;
+    if (np == 0) return;
+    if (!b->obs_offset) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null obs_offset"};
+    if (!pts_out || !status) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    if (b->obs_offset[0] != 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "obs_offset[0] != 0"};
+    for (int p = 0; p < np; ++p)
+      if (b->obs_offset[p + 1] < b->obs_offset[p])
+        throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "obs_offset decreases at point " + std::to_string(p)};
+    const size_t no = (size_t)b->obs_offset[np];
+    if (no > 0 && (!b->obs_cam || !b->obs_uv)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null observation array"};
+    if (nc > 0 && (!b->extr || !b->K)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null camera array (extr, K)"};
+    if (nc > (int)(0x7fffffff / kTriRec)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "too many cameras"};
+    if (t.init == BA_TRI_INIT_GIVEN && !b->pts_init)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "init is BA_TRI_INIT_GIVEN but pts_init is null"};
+    if ((t.checks & BA_TRI_CHECK_SCALE) && no > 0 && !b->cam_center)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "the scale test is on but cam_center is null"};
+    for (size_t k = 0; k < no; ++k)
+      if (b->obs_cam[k] < 0 || b->obs_cam[k] >= nc)
+        throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "obs_cam[" + std::to_string(k) + "] = " + std::to_string(b->obs_cam[k]) +
+                                                   " out of range (" + std::to_string(nc) + " cameras)"};
+    const double t0 = now_s();
+    const bool given = t.init == BA_TRI_INIT_GIVEN, has_ctr = b->cam_center != nullptr, has_scale = b->obs_scale != nullptr;
+    // ---- one buffer: inputs (uploaded) | outputs (downloaded) | scratch
+    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+    size_t at = 0;
+    auto sec = [&](size_t bytes) { const size_t r = at; at += al(bytes); return r; };
+    const size_t o_extr = sec(sizeof(float) * 16 * nc), o_ctr = sec(has_ctr ? sizeof(float) * 3 * nc : 0),
+                 o_K = sec(sizeof(float) * 9 * nc), o_off = sec(sizeof(int) * ((size_t)np + 1)),
+                 o_oc = sec(sizeof(int) * no), o_uv = sec(sizeof(float) * 2 * no),
+                 o_sc = sec(has_scale ? sizeof(float) * no : 0), o_init = sec(given ? sizeof(double) * 3 * np : 0);
+    const size_t in_b = at;
+    const size_t o_pts = sec(sizeof(double) * 3 * np), o_sum = sec(sizeof(double) * 6 * np), o_st = sec((size_t)np);
+    const size_t io_b = at;
+    const size_t w_rec = sec(sizeof(double) * kTriRec * nc);
+    const size_t total = at;
+    HIP_OK(hipSetDevice(ctx->device));
+    if (total > ctx->tri_cap) {
+      if (ctx->tri_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->tri_buf); }
+      ctx->tri_buf = nullptr;
+      ctx->tri_cap = 0;
+      const hipError_t e = hipMalloc(&ctx->tri_buf, total);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();   // (not sticky: the context stays usable)
+        ctx->tri_buf = nullptr;
+        throw BaError{e == hipErrorOutOfMemory ? BA_ERR_OUT_OF_MEMORY : BA_ERR_DEVICE,
+                      fn + "scratch of " + std::to_string(total) + " bytes: " + hipGetErrorString(e)};
+      }
+      ctx->tri_cap = total;
+    }
+    std::vector<char>& h = ctx->tri_host;
+    h.resize(io_b);
+    auto put = [&](size_t off, const void* src, size_t nb) { if (nb) std::memcpy(h.data() + off, src, nb); };
+    put(o_extr, b->extr, sizeof(float) * 16 * nc);
+    if (has_ctr) put(o_ctr, b->cam_center, sizeof(float) * 3 * nc);
+    put(o_K, b->K, sizeof(float) * 9 * nc);
+    put(o_off, b->obs_offset, sizeof(int) * ((size_t)np + 1));
+    put(o_oc, b->obs_cam, sizeof(int) * no);
+    put(o_uv, b->obs_uv, sizeof(float) * 2 * no);
+    if (has_scale) put(o_sc, b->obs_scale, sizeof(float) * no);
+    if (given) put(o_init, b->pts_init, sizeof(double) * 3 * np);
+    char* d = ctx->tri_buf;
+    HIP_OK(hipMemcpyAsync(d, h.data(), in_b, hipMemcpyHostToDevice, ctx->stream));
+    TriArgs A{};
+    A.n_pts = np; A.n_cams = nc;
+    A.init_given = given; A.refine = t.refine; A.min_views = t.min_views; A.checks = t.checks;
+    A.behind_any = t.behind_rule;
+    A.huber_a = b->huber_a;
+    auto df = [&](size_t off) { return reinterpret_cast<const float*>(d + off); };
+    A.extr = df(o_extr); A.center = has_ctr ? df(o_ctr) : nullptr; A.K = df(o_K);
+    A.off = reinterpret_cast<const int*>(d + o_off); A.obs_cam = reinterpret_cast<const int*>(d + o_oc);
+    A.uv = reinterpret_cast<const float2*>(d + o_uv);
+    A.scale = has_scale ? df(o_sc) : nullptr;
+    A.pts_init = given ? reinterpret_cast<const double*>(d + o_init) : nullptr;
+    A.rec = reinterpret_cast<double*>(d + w_rec);
+    A.pts_out = reinterpret_cast<double*>(d + o_pts);
+    A.summ = reinterpret_cast<double*>(d + o_sum);
+    A.status = reinterpret_cast<uint8_t*>(d + o_st);
+    PoseOpts po{o.max_num_iterations, o.max_num_consecutive_invalid_steps, o.jacobi_scaling,
+                o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance, o.initial_trust_region_radius,
+                o.max_trust_region_radius, o.min_trust_region_radius, o.min_relative_decrease, o.min_lm_diagonal,
+                o.max_lm_diagonal};
+    const double t_prep = now_s() - t0;
+    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
+    launch_triangulate(A, po, ctx->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
+    HIP_OK(hipMemcpyAsync(h.data() + in_b, d + in_b, io_b - in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    float kernel_ms = 0.0f;
+    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
+    std::memcpy(pts_out, h.data() + o_pts, sizeof(double) * 3 * np);
+    std::memcpy(status, h.data() + o_st, (size_t)np);
+    const double wall = now_s() - t0;
+    ctx->tri_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * wall};
+    if (summaries) {
+      const double* sm = reinterpret_cast<const double*>(h.data() + o_sum);
+      for (int i = 0; i < np; ++i) {
+        ba_summary S{};
+        S.initial_cost = sm[6 * (size_t)i];
+        S.final_cost = sm[6 * (size_t)i + 1];
+        S.num_iterations = (int)sm[6 * (size_t)i + 2];
+        S.num_successful_steps = (int)sm[6 * (size_t)i + 3];
+        S.num_unsuccessful_steps = (int)sm[6 * (size_t)i + 4];
+        S.termination_type = (int)sm[6 * (size_t)i + 5];
+        S.total_time_s = S.linearize_time_s = S.solve_time_s = wall;
+        summaries[i] = S;
+      }
+    }
+  });
+}
+
+int ba_triangulate_times(ba_ctx* ctx, double* ms, int n) {
+  if (!ctx) return -BA_ERR_INVALID_ARGUMENT;
+  const int m = (int)ctx->tri_ms.size();
+  for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = ctx->tri_ms[i];
   return m;
 }
 

@@ -421,3 +421,39 @@ def shard_bounds(problem: Problem, nranks: int) -> list[int]:
     b = [int(np.searchsorted(csum, total * r / nranks, side="left")) for r in range(nranks + 1)]
     b[0], b[-1] = 0, problem.n_pts
     return b
+
+
+@dataclass
+class TriangulationBatch:
+    """The arrays of the C-ABI's ba_tri_batch: point p owns observations
+    [obs_offset[p], obs_offset[p+1]), in the caller's order within a point."""
+    extr: np.ndarray         # (C, 16) float32, column-major world->camera
+    cam_center: np.ndarray   # (C, 3) float32 camera centres in the world (getWorldPos)
+    K: np.ndarray            # (C, 9) float32
+    obs_offset: np.ndarray   # (P + 1,) int32
+    obs_cam: np.ndarray      # (N,) int32
+    obs_uv: np.ndarray       # (N, 2) float32
+    pts: np.ndarray          # (P, 3) float64: the problem's points (a start for TRI_INIT_GIVEN)
+    order: np.ndarray        # (N,) the problem's observation index of each batch observation
+    huber_a: float = HUBER_A
+
+
+def triangulation_batch(problem: Problem) -> TriangulationBatch:
+    """A Problem whose cameras are all constant as the batch arrays of
+    Solver.triangulate: observations sorted by point (stable: a point's first
+    observation stays its first), offsets, the float extrinsics and the camera
+    centres -R^T t derived from them."""
+    p = problem.normalized()
+    if p.cam_fixed is None or p.cam_fixed_extr is None or not np.all(p.cam_fixed != 0):
+        raise ValueError("triangulation_batch: every camera must be constant (fix_camera)")
+    order = np.argsort(p.obs_pt, kind="stable")
+    cnt = np.bincount(p.obs_pt, minlength=p.n_pts).astype(np.int64)
+    off = np.zeros(p.n_pts + 1, np.int64)
+    np.cumsum(cnt, out=off[1:])
+    E = p.cam_fixed_extr.reshape(-1, 4, 4).transpose(0, 2, 1).astype(np.float64)   # [row, col]
+    center = -np.einsum("cji,cj->ci", E[:, :3, :3], E[:, :3, 3])
+    return TriangulationBatch(
+        extr=p.cam_fixed_extr.copy(), cam_center=np.ascontiguousarray(center, dtype=np.float32), K=p.K.copy(),
+        obs_offset=off.astype(np.int32), obs_cam=np.ascontiguousarray(p.obs_cam[order]),
+        obs_uv=np.ascontiguousarray(p.obs_uv[order]), pts=p.pts.copy(), order=order.astype(np.int64),
+        huber_a=float(p.huber_a))

@@ -445,6 +445,68 @@ class Solver:
             self.lib.ba_window_times(self.h, _ptr(out), n)
         return out
 
+    def triangulate(self, extr, K, obs_offset, obs_cam, obs_uv, *, cam_center=None, obs_scale=None, pts_init=None,
+                    refine: bool = False, options: Options | None = None, huber_a: float = HUBER_A,
+                    min_views: int = 2, checks: int = N.TRI_CHECK_ALL, behind_rule: int = 0, init: int | None = None,
+                    with_summaries: bool | None = None
+                    ) -> tuple[np.ndarray, np.ndarray, list[Summary] | None]:
+        """Batched multi-view triangulation (ba_triangulate): SfMHelper::
+        triangulatePoints for any number of views per point, optionally with a
+        per-point LM refinement against the constant cameras, in one launch.
+        extr [C, 16] (col-major world->camera), K [C, 9]; point p owns
+        observations [obs_offset[p], obs_offset[p+1]) of obs_cam / obs_uv;
+        cam_center [C, 3] and obs_scale [N] (1.2^octave; None: all 1) feed the
+        scale test, pts_init [P, 3] starts from the caller's points instead of
+        the DLT (init overrides the choice: N.TRI_INIT_DLT / TRI_INIT_GIVEN).
+        checks: N.TRI_CHECK_* bits; behind_rule 0: behind every camera (the
+        reference's), 1: behind any.  Returns (pts [P, 3] float64, status [P]
+        uint8 (N.TRI_*), summaries or None); summaries default to refine."""
+        e = np.ascontiguousarray(extr, dtype=np.float32).reshape(-1, 16)
+        k = np.ascontiguousarray(K, dtype=np.float32).reshape(-1, 9)
+        off = np.ascontiguousarray(obs_offset, dtype=np.int32).reshape(-1)
+        oc = np.ascontiguousarray(obs_cam, dtype=np.int32).reshape(-1)
+        uv = np.ascontiguousarray(obs_uv, dtype=np.float32).reshape(-1, 2)
+        ctr = None if cam_center is None else np.ascontiguousarray(cam_center, dtype=np.float32).reshape(-1, 3)
+        sc = None if obs_scale is None else np.ascontiguousarray(obs_scale, dtype=np.float32).reshape(-1)
+        x0 = None if pts_init is None else np.ascontiguousarray(pts_init, dtype=np.float64).reshape(-1, 3)
+        n = max(off.size - 1, 0)
+        if k.shape[0] != e.shape[0] or (ctr is not None and ctr.shape[0] != e.shape[0]):
+            raise ValueError("triangulate: extr, K and cam_center disagree on the number of cameras")
+        if uv.shape[0] != oc.size or (sc is not None and sc.size != oc.size) or (n and off[-1] > oc.size):
+            raise ValueError("triangulate: obs_cam, obs_uv, obs_scale and obs_offset disagree on the number of observations")
+        if x0 is not None and x0.shape[0] != n:
+            raise ValueError("triangulate: pts_init must have one row per point")
+        b = N.ba_tri_batch(n_cams=e.shape[0], n_pts=n, extr=_ptr(e), cam_center=_ptr(ctr), K=_ptr(k),
+                           obs_offset=_ptr(off), obs_cam=_ptr(oc), obs_uv=_ptr(uv), obs_scale=_ptr(sc),
+                           pts_init=_ptr(x0), huber_a=float(huber_a))
+        if init is None:
+            init = N.TRI_INIT_GIVEN if x0 is not None else N.TRI_INIT_DLT
+        t = N.ba_tri_options(init=int(init), refine=int(refine), min_views=int(min_views), checks=int(checks),
+                             behind_rule=int(behind_rule), reserved=0)
+        o = (options or Options()).to_c()
+        pts = np.zeros((n, 3))
+        status = np.zeros(n, np.uint8)
+        want = bool(refine) if with_summaries is None else bool(with_summaries)
+        sums = (N.ba_summary * max(n, 1))() if want else None
+        self._check(self.lib.ba_triangulate(self.h, C.byref(b), C.byref(t), C.byref(o), _ptr(pts), _ptr(status), sums),
+                    "ba_triangulate")
+        res = None
+        if want:
+            res = [Summary(s.initial_cost, s.final_cost, s.num_iterations, s.num_successful_steps,
+                           s.num_unsuccessful_steps,
+                           N.TERMINATION_NAMES.get(s.termination_type, str(s.termination_type)),
+                           s.total_time_s, s.linearize_time_s, s.solve_time_s) for s in list(sums)[:n]]
+        return pts, status, res
+
+    def triangulate_times(self) -> np.ndarray:
+        """Times (ms) of the last triangulate: host preparation (wall), the
+        kernels (device), the whole call (wall)."""
+        n = self.lib.ba_triangulate_times(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            self.lib.ba_triangulate_times(self.h, _ptr(out), n)
+        return out
+
     def synchronize(self):
         self._check(self.lib.ba_synchronize(self.h), "ba_synchronize")
 

@@ -339,6 +339,112 @@ int ba_get_window_iteration_log(ba_ctx* ctx, int problem, ba_iteration* out, int
  * returns 3 (0 before the first call).  Diagnostic. */
 int ba_window_times(ba_ctx* ctx, double* ms, int n);
 
+/* Batched multi-view triangulation with structure-only refinement: the
+ * creation of map points.  Replaces SfMHelper::triangulatePoints
+ * (SfMHelper.cpp:759-878: cv::triangulatePoints, then three float acceptance
+ * tests per point) for any number of views per point, and is the dual of
+ * ba_solve_pose_batch: many points, each refined independently against
+ * constant cameras, in one kernel launch (a fixed group of 8 lanes per point).
+ * Point p owns observations [obs_offset[p], obs_offset[p+1]).
+ *
+ * Initialisation (init == BA_TRI_INIT_DLT): per view P = K E(0:3, :) in double
+ * from the float values, the rows u P2 - P0 and v P2 - P1 (the construction of
+ * cv::triangulatePoints), M = A^T A (4x4, fp64, fixed summation order), the
+ * eigenvector v of M's smallest eigenvalue by cyclic Jacobi rotations (pair
+ * order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a sweep starts only while the
+ * squared off-diagonal mass exceeds 1e-36 of the squared diagonal mass, at
+ * most 16 sweeps), X = v[0:3] / v[3] (independent of v's sign).  When the
+ * second smallest eigenvalue is <= 1e-12 of the largest (all rays coincide:
+ * no point is determined) X is NaN.  BA_TRI_INIT_GIVEN starts from pts_init.
+ *
+ * Refinement (refine == 1): point p is solved as ba_set_problem + ba_solve
+ * (BA_DENSE_SCHUR, BA_FP64) + ba_get_params would solve the ba_problem with
+ * all n_cams cameras constant (cam_fixed_extr = extr), one variable point at
+ * the start value and the point's observations (PointOnlyReprojectionError,
+ * HuberLoss(huber_a), Jacobi scaling from iteration 0, the clamped LM
+ * diagonal, the same termination rules, invalid-step handling and radius
+ * updates; opt = the LM options).  A camera may observe a point more than
+ * once: each observation counts.  Non-convergence is reported in the summary
+ * only.
+ *
+ * Acceptance tests, in the reference's order on the float-rounded result
+ * (float)X with ba_prune's pinned float arithmetic; the first failing test
+ * gives the status:
+ *   camCoord = hnormalized(extr [X;1]); cheirality: z <= 0 in every view
+ *   (behind_rule 0, the reference's `&&`) or in any view (behind_rule 1);
+ *   chi2: |hnormalized(K camCoord) - uv| * invSigma > 5.991f in any view (a
+ *   norm, not a squared norm, as in ba_prune), invSigma = (float)(1.0 /
+ *   (double)obs_scale);
+ *   scale: view 0 (the point's first observation) against every other view
+ *   j, with d = |X - cam_center|: rejected if d_0 == 0 || d_j == 0, if
+ *   (d_0 / d_j) * 1.5f < s_j / s_0, or if d_0 / d_j > (s_j / s_0) * 1.5f.
+ * With two views and the defaults this is triangulatePoints line for line.
+ *
+ * pts_out[3*n_pts] receives the (refined) points in double, status[n_pts] a
+ * ba_tri_status each, summaries[n_pts] (may be NULL; meaningful when refine)
+ * the per-point summary (time fields: the call's wall time).  A FEW_VIEWS
+ * point is returned as pts_init (GIVEN) or zeros (DLT), its summary is
+ * BA_CONVERGENCE with 0 iterations.  A point's output bits depend only on its
+ * own observations, the cameras and the options, not on its place in the
+ * batch or on the other points; two calls give bitwise equal output.  The
+ * call does not touch the context's current problem (a ba_solve before and
+ * after is bit for bit what it would have been), uses no collective and
+ * blocks until the results are on the host.
+ *
+ * Errors (the context stays usable; nothing is launched; all validation is on
+ * the host):
+ *   BA_ERR_INVALID_ARGUMENT  a NULL required array, obs_offset[0] != 0 or a
+ *                            decreasing obs_offset (the message names the
+ *                            point), obs_cam out of range (names the
+ *                            observation), init GIVEN without pts_init, the
+ *                            scale test without cam_center, unknown option
+ *                            values; with refine: linear_solver !=
+ *                            BA_DENSE_SCHUR or precision != BA_FP64,
+ *   BA_ERR_OUT_OF_MEMORY     the scratch cannot be allocated. */
+enum ba_tri_status {
+  BA_TRI_OK = 0,
+  BA_TRI_FEW_VIEWS = 1,    /* fewer than max(2, min_views) observations */
+  BA_TRI_DEGENERATE = 2,   /* non-finite point (homogeneous w == 0, coincident rays, ...) or the refinement ended BA_FAILURE */
+  BA_TRI_BEHIND = 3,       /* SfMHelper.cpp:806-813 */
+  BA_TRI_CHI2 = 4,         /* :815-838 */
+  BA_TRI_SCALE = 5         /* :840-858 */
+};
+enum ba_tri_init { BA_TRI_INIT_DLT = 0, BA_TRI_INIT_GIVEN = 1 };
+enum ba_tri_check { BA_TRI_CHECK_CHEIRALITY = 1, BA_TRI_CHECK_CHI2 = 2, BA_TRI_CHECK_SCALE = 4 };
+
+typedef struct {
+  int32_t n_cams, n_pts;
+  const float*   extr;        /* [16*n_cams] col-major world->camera = getPose().inverse() (as ba_prune_problem) */
+  const float*   cam_center;  /* [3*n_cams]  getWorldPos(); may be NULL when the scale test is off */
+  const float*   K;           /* [9*n_cams]  col-major */
+  const int32_t* obs_offset;  /* [n_pts+1], [0] = 0, non-decreasing */
+  const int32_t* obs_cam;     /* [n_obs] */
+  const float*   obs_uv;      /* [2*n_obs] */
+  const float*   obs_scale;   /* [n_obs] (float)pow(1.2, octave); NULL = all 1 */
+  const double*  pts_init;    /* [3*n_pts]; read when init == BA_TRI_INIT_GIVEN */
+  double huber_a;             /* refinement loss, as ba_pose_batch */
+} ba_tri_batch;
+
+typedef struct {
+  int32_t init;        /* BA_TRI_INIT_DLT (default) | BA_TRI_INIT_GIVEN */
+  int32_t refine;      /* 0 (default: the reference's path) | 1: per-point LM */
+  int32_t min_views;   /* default 2 */
+  int32_t checks;      /* ba_tri_check bits; default all three */
+  int32_t behind_rule; /* 0 (default, the reference's): z <= 0 in EVERY view; 1: in ANY view */
+  int32_t reserved;
+} ba_tri_options;
+
+void ba_triangulate_defaults(ba_tri_options* opt);
+int ba_triangulate(ba_ctx* ctx, const ba_tri_batch* batch, const ba_tri_options* topt /* NULL = defaults */,
+                   const ba_options* opt /* LM options, NULL = defaults; read when refine */,
+                   double* pts_out /* [3*n_pts] */, uint8_t* status /* [n_pts] */,
+                   ba_summary* summaries /* [n_pts], may be NULL */);
+/* Times (ms) of the last successful ba_triangulate: [0] host preparation
+ * (validation, staging, upload enqueue; wall), [1] the kernels (device, HIP
+ * events), [2] the whole call (wall).  Copies min(n, 3) values, returns 3 (0
+ * before the first call).  Diagnostic. */
+int ba_triangulate_times(ba_ctx* ctx, double* ms, int n);
+
 /* Test / inspection entry point: the state inside ceres::Solve's
  * SchurComplementSolver (Optimizer.cpp:242, DENSE_SCHUR) for one step.
  * Linearises at the current parameters with iteration-0 Jacobi scaling, then
