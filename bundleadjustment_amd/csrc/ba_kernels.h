@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "../host/ba_batch_pack.hpp"   // WinProb (host-only packer of the batch entry points)
+
 namespace bahip {
 
 constexpr int kThreads = 256;
@@ -298,15 +300,6 @@ constexpr int kWinMaxCams = 16;    // = BA_WINDOW_MAX_CAMS: variable observed ca
 // doubles per camera table row, value-only camera record and observation
 // record of the scratch (= kTblRec, kRecL, kJR of the device headers)
 constexpr int kWinTbl = 42, kWinVRec = 48, kWinJR = 20;
-struct WinProb {
-  int cam0, pt0, obs0;             // first camera / point / observation of the problem in the concatenated arrays
-  int nc, np, no, nvc;
-  int vc0;                         // first compact variable camera (sum of nvc of the problems before)
-  int poff0;                       // pt_off + poff0: [np + 1] CSR of the observations by point
-  int coff0;                       // cam_off + coff0: [nvc + 1] CSR of cam_obs by compact variable camera
-  int vobs0;                       // cam_obs + vobs0: observations of variable cameras, grouped by camera
-  int pad;
-};
 struct WinArgs {
   const WinProb* prob;
   size_t NC, NP, NO, NV;           // totals over the batch (strides of the double-buffered scratch)

@@ -1,6 +1,8 @@
 // ba_solver.hip — host side of libba_hip.so: problem structure, device
 // workspace, the Levenberg-Marquardt driver and the extern "C" ABI
-// (include/ba_hip.h).
+// (include/ba_hip.h).  The batch entry points stage through StagingArena; their
+// host-only packing (the error type, section layout, offset checks, the window
+// structure build) is host/ba_batch_pack.hpp.
 //
 // The driver restates ceres::TrustRegionMinimizer + LevenbergMarquardtStrategy
 // with the options of BAOptimizer::configureSolver (reference
@@ -38,11 +40,7 @@ using namespace bahip;
 
 namespace {
 
-struct BaError {
-  int code;
-  std::string msg;
-};
-
+// BaError {code, msg}: host/ba_batch_pack.hpp (through ba_kernels.h)
 #define HIP_OK(expr)                                                                                  \
   do {                                                                                                \
     hipError_t _e = (expr);                                                                           \
@@ -59,6 +57,19 @@ struct BaError {
 double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+
+// One staging buffer of a batch entry point: device memory (inputs | outputs |
+// scratch) grown on demand and reused across calls, and the host copy of its
+// inputs / outputs
+struct StagingArena {
+  char* dev = nullptr;
+  size_t cap = 0;
+  std::vector<char> host;
+  void reserve(ba_ctx* ctx, size_t bytes, const std::string& fn);
+};
+
+// hipFree at scope exit (buffers that live for one call)
+struct DevFree { void* p; ~DevFree() { (void)hipFree(p); } };
 
 }  // namespace
 
@@ -98,24 +109,15 @@ struct ba_ctx {
   unsigned* d_hseq = nullptr;
   unsigned* d_ticket = nullptr;  // k_reduce<true>'s last-workgroup ticket (zero between launches)
   unsigned scal_seq = 0;
-  char* pose_buf = nullptr;      // ba_solve_pose_batch device staging (grown on demand)
-  size_t pose_cap = 0;
-  std::vector<char> pose_host;
-  // ba_solve_window_batch: device staging + scratch (grown on demand, reused
-  // across calls), the host copy of its inputs / outputs, the last call's logs
-  char* win_buf = nullptr;
-  size_t win_cap = 0;
-  std::vector<char> win_host;
+  // staging of ba_solve_pose_batch, ba_solve_window_batch and ba_triangulate
+  // (one each: a call of one never makes another reallocate)
+  StagingArena pose, win, tri;
+  // ba_solve_window_batch: the last call's logs and times
   std::vector<ba_iteration> win_log;   // [n_problems][win_log_cap]
   std::vector<int> win_log_n;
   int win_log_cap = 0;
   std::vector<double> win_ms;          // ba_window_times of the last call
-  // ba_triangulate: device staging + camera scratch (grown on demand, reused
-  // across calls), the host copy of its inputs / outputs, the last call's times
-  char* tri_buf = nullptr;
-  size_t tri_cap = 0;
-  std::vector<char> tri_host;
-  std::vector<double> tri_ms;
+  std::vector<double> tri_ms;          // ba_triangulate_times of the last call
 
   // host copies of the sorted structure, kept for the lazily built
   // linear-solver structures (Schur pair lists / PCG duplicate pairs)
@@ -294,6 +296,45 @@ struct ba_ctx {
 };
 
 namespace {
+
+// Room for `bytes`.  Growing waits for the stream before it frees the old
+// buffer; a failed allocation leaves the arena empty and no sticky error, so
+// the context stays usable.
+void StagingArena::reserve(ba_ctx* ctx, size_t bytes, const std::string& fn) {
+  if (bytes <= cap) return;
+  if (dev) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(dev); }
+  dev = nullptr; cap = 0;
+  const hipError_t e = hipMalloc(&dev, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    dev = nullptr;
+    throw BaError{e == hipErrorOutOfMemory ? BA_ERR_OUT_OF_MEMORY : BA_ERR_DEVICE,
+                  fn + "scratch of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e)};
+  }
+  cap = bytes;
+}
+
+template <class T> T* at(char* base, size_t off) { return reinterpret_cast<T*>(base + off); }
+// a section of a staging buffer's host copy
+void stage(std::vector<char>& h, size_t off, const void* src, size_t nb) { if (nb) std::memcpy(h.data() + off, src, nb); }
+
+ba_options options_or_default(const ba_options* opt) {
+  ba_options o;
+  if (opt) o = *opt; else ba_default_options(&o);
+  return o;
+}
+PoseOpts pose_opts(const ba_options& o) {
+  return PoseOpts{o.max_num_iterations, o.max_num_consecutive_invalid_steps, o.jacobi_scaling,
+                  o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance, o.initial_trust_region_radius,
+                  o.max_trust_region_radius, o.min_trust_region_radius, o.min_relative_decrease, o.min_lm_diagonal,
+                  o.max_lm_diagonal};
+}
+// the *_times getters: up to n values into ms, returns how many there are
+int copy_times(const std::vector<double>& t, double* ms, int n) {
+  const int m = (int)t.size();
+  for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = t[i];
+  return m;
+}
 
 // ---------------------------------------------------------------------------
 // structure build
@@ -1202,8 +1243,7 @@ void check_options(const ba_options& o) {
 // ---------------------------------------------------------------------------
 void solve(ba_ctx* ctx, const ba_options* opt, ba_summary* sum) {
   if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, "ba_solve before ba_set_problem"};
-  ba_options o;
-  if (opt) o = *opt; else ba_default_options(&o);
+  ba_options o = options_or_default(opt);
   check_options(o);
   ctx->read_env();
   const double t0 = now_s();
@@ -1460,8 +1500,7 @@ void covariance(ba_ctx* ctx, const ba_covariance_request_ex* rx, const std::stri
     }
   }
   HIP_OK(hipSetDevice(ctx->device));
-  ba_options o;
-  ba_default_options(&o);   // DENSE_SCHUR, fp64
+  ba_options o = options_or_default(nullptr);   // DENSE_SCHUR, fp64
   ctx->read_env();
   const hipStream_t s = ctx->stream;
   struct Events {
@@ -1677,8 +1716,7 @@ void covariance_iterative(ba_ctx* ctx, const ba_covariance_request* req, const b
   }
   const int R = 6 * B;
   HIP_OK(hipSetDevice(ctx->device));
-  ba_options o;
-  ba_default_options(&o);
+  ba_options o = options_or_default(nullptr);
   ctx->read_env();
   const hipStream_t s = ctx->stream;
   struct Events {
@@ -1845,8 +1883,7 @@ void covariance_iterative_bench(ba_ctx* ctx, int cols, int reps, int warmup, dou
   if ((cols != 0 && cols != 1 && cols != 2 && cols != 4) || reps < 1 || warmup < 0 || !ms || ctx->nvc == 0)
     throw BaError{BA_ERR_INVALID_ARGUMENT, fn + ": bad arguments"};
   HIP_OK(hipSetDevice(ctx->device));
-  ba_options o;
-  ba_default_options(&o);
+  ba_options o = options_or_default(nullptr);
   ctx->read_env();
   const hipStream_t s = ctx->stream;
   const LinResult L = linearize(ctx, true, o.min_lm_diagonal, o.max_lm_diagonal);
@@ -2057,9 +2094,7 @@ int ba_destroy(ba_ctx* ctx) {
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
-  if (ctx->pose_buf) (void)hipFree(ctx->pose_buf);
-  if (ctx->win_buf) (void)hipFree(ctx->win_buf);
-  if (ctx->tri_buf) (void)hipFree(ctx->tri_buf);
+  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri}) (void)hipFree(a->dev);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -2158,12 +2193,12 @@ int ba_eval_residuals(ba_ctx* ctx, double* r, double* cost) {
     const int no = ctx->no;
     double* d_r = nullptr;
     HIP_OK(hipMalloc(&d_r, sizeof(double) * 2 * std::max(no, 1)));
+    DevFree guard{d_r};
     launch_cam_prep(ctx->P, ctx->W.cams, ctx->W.rec_c, false, ctx->stream);
     launch_residuals(ctx->P, ctx->W.rec_c, ctx->W.pts, d_r, ctx->stream);
     std::vector<double> rs(2 * (size_t)no);
     HIP_OK(hipMemcpyAsync(rs.data(), d_r, sizeof(double) * 2 * no, hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d_r);
     double c = 0.0;
     const double a = ctx->huber_a, b = a * a;
     for (int s = 0; s < no; ++s) {
@@ -2181,8 +2216,7 @@ int ba_linearize(ba_ctx* ctx, double* r, double* J, double* cost) {
   return guarded(ctx, [&] {
     if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, "no problem"};
     HIP_OK(hipSetDevice(ctx->device));
-    ba_options o;
-    ba_default_options(&o);
+    ba_options o = options_or_default(nullptr);
     LinResult L = linearize(ctx, true, o.min_lm_diagonal, o.max_lm_diagonal);
     const int no = ctx->no;
     if (ctx->W.jrfree) {   // the iteration never stores J: write the records once for the read-back
@@ -2231,32 +2265,33 @@ int ba_prune(ba_ctx* ctx, const ba_prune_problem* p, uint8_t* result) {
         throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_prune: obs_cam[" + std::to_string(o) + "] out of range"};
     HIP_OK(hipSetDevice(ctx->device));
     // one staging buffer: cameras (16 + 3 + 9 floats) then pairs (1 int + 3 + 2 + 1 + 2 floats + 1 byte)
-    const size_t cam_b = sizeof(float) * 28 * (size_t)nc, obs_b = sizeof(float) * 9 * (size_t)no;
-    const size_t bytes = cam_b + obs_b + sizeof(int) * (size_t)no + (size_t)no;
+    SectionLayout L(1);   // (packed: every section is a multiple of its element size)
+    const size_t NC = nc, NO = no;
+    const size_t o_extr = L.add(sizeof(float) * 16 * NC), o_ctr = L.add(sizeof(float) * 3 * NC),
+                 o_K = L.add(sizeof(float) * 9 * NC), o_X = L.add(sizeof(float) * 3 * NO),
+                 o_uv = L.add(sizeof(float) * 2 * NO), o_sig = L.add(sizeof(float) * NO),
+                 o_dist = L.add(sizeof(float) * 2 * NO), o_cam = L.add(sizeof(int) * NO);
+    L.end_inputs();
+    const size_t o_res = L.add(NO);
     char* d = nullptr;
-    HIP_OK(hipMalloc(&d, bytes));
-    std::vector<char> h(bytes - (size_t)no);
-    size_t off = 0;
-    auto put = [&](const void* src, size_t n) { std::memcpy(h.data() + off, src, n); off += n; };
-    put(p->extr, sizeof(float) * 16 * nc);
-    put(p->cam_center, sizeof(float) * 3 * nc);
-    put(p->K, sizeof(float) * 9 * nc);
-    put(p->obs_X, sizeof(float) * 3 * no);
-    put(p->obs_uv, sizeof(float) * 2 * no);
-    put(p->obs_inv_sigma, sizeof(float) * no);
-    put(p->obs_dist, sizeof(float) * 2 * no);
-    put(p->obs_cam, sizeof(int) * no);
-    auto f = [&](size_t o) { return reinterpret_cast<const float*>(d + o); };
-    const size_t oX = cam_b, oUV = oX + sizeof(float) * 3 * no, oS = oUV + sizeof(float) * 2 * no,
-                 oD = oS + sizeof(float) * no, oC = oD + sizeof(float) * 2 * no, oR = oC + sizeof(int) * no;
-    HIP_OK(hipMemcpyAsync(d, h.data(), h.size(), hipMemcpyHostToDevice, ctx->stream));
-    launch_prune(no, f(0), f(sizeof(float) * 16 * nc), f(sizeof(float) * 19 * nc),
-                 reinterpret_cast<const int*>(d + oC), f(oX), f(oUV), f(oS), f(oD),
-                 reinterpret_cast<uint8_t*>(d + oR), ctx->stream);
+    HIP_OK(hipMalloc(&d, L.total));
+    DevFree guard{d};
+    std::vector<char> h(L.in_b);
+    stage(h, o_extr, p->extr, sizeof(float) * 16 * NC);
+    stage(h, o_ctr, p->cam_center, sizeof(float) * 3 * NC);
+    stage(h, o_K, p->K, sizeof(float) * 9 * NC);
+    stage(h, o_X, p->obs_X, sizeof(float) * 3 * NO);
+    stage(h, o_uv, p->obs_uv, sizeof(float) * 2 * NO);
+    stage(h, o_sig, p->obs_inv_sigma, sizeof(float) * NO);
+    stage(h, o_dist, p->obs_dist, sizeof(float) * 2 * NO);
+    stage(h, o_cam, p->obs_cam, sizeof(int) * NO);
+    HIP_OK(hipMemcpyAsync(d, h.data(), L.in_b, hipMemcpyHostToDevice, ctx->stream));
+    launch_prune(no, at<const float>(d, o_extr), at<const float>(d, o_ctr), at<const float>(d, o_K),
+                 at<const int>(d, o_cam), at<const float>(d, o_X), at<const float>(d, o_uv),
+                 at<const float>(d, o_sig), at<const float>(d, o_dist), at<uint8_t>(d, o_res), ctx->stream);
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(result, d + oR, (size_t)no, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipMemcpyAsync(result, d + o_res, NO, hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d);
   });
 }
 
@@ -2269,80 +2304,49 @@ int ba_solve_pose_batch(ba_ctx* ctx, const ba_pose_batch* b, const ba_options* o
     if (n == 0) return;
     if (!b->obs_offset || !b->cams || !b->K || !cams_out)
       throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_solve_pose_batch: null array"};
-    if (b->obs_offset[0] != 0) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_solve_pose_batch: obs_offset[0] != 0"};
-    for (int i = 0; i < n; ++i)
-      if (b->obs_offset[i + 1] < b->obs_offset[i])
-        throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_solve_pose_batch: obs_offset decreases at " + std::to_string(i)};
-    const int no = b->obs_offset[n];
-    if (no > 0 && (!b->pts || !b->obs_uv)) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_solve_pose_batch: null array"};
-    ba_options o;
-    if (opt) o = *opt; else ba_default_options(&o);
-    PoseOpts po{o.max_num_iterations, o.max_num_consecutive_invalid_steps, o.jacobi_scaling,
-                o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance, o.initial_trust_region_radius,
-                o.max_trust_region_radius, o.min_trust_region_radius, o.min_relative_decrease, o.min_lm_diagonal,
-                o.max_lm_diagonal};
+    const std::string fn = "ba_solve_pose_batch: ";
+    check_offsets(fn.c_str(), "obs_offset", b->obs_offset, n);
+    const size_t N = n, NO = b->obs_offset[n];
+    if (NO > 0 && (!b->pts || !b->obs_uv)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null array"};
+    const PoseOpts po = pose_opts(options_or_default(opt));
     const double t0 = now_s();
     HIP_OK(hipSetDevice(ctx->device));
     // one staging buffer, 16-B aligned sections: inputs (uploaded), then outputs
-    auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
-    const size_t s_off = al(sizeof(int) * (n + 1)), s_cam = al(sizeof(double) * 6 * n), s_K = al(sizeof(float) * 9 * n),
-                 s_X = al(sizeof(double) * 3 * (size_t)no), s_uv = al(sizeof(float) * 2 * (size_t)no);
-    const size_t in_b = s_off + s_cam + s_K + s_X + s_uv;
-    const size_t out_b = s_cam + al(sizeof(double) * 8 * n);
-    if (in_b + out_b > ctx->pose_cap) {
-      if (ctx->pose_buf) (void)hipFree(ctx->pose_buf);
-      ctx->pose_buf = nullptr;
-      ctx->pose_cap = 0;
-      HIP_OK(hipMalloc(&ctx->pose_buf, in_b + out_b));
-      ctx->pose_cap = in_b + out_b;
-    }
-    std::vector<char>& h = ctx->pose_host;
-    h.assign(in_b + out_b, 0);
-    size_t at = 0;
-    auto put = [&](const void* src, size_t nb, size_t sec) { if (nb) std::memcpy(h.data() + at, src, nb); at += sec; };
-    put(b->obs_offset, sizeof(int) * (n + 1), s_off);
-    put(b->cams, sizeof(double) * 6 * n, s_cam);
-    put(b->K, sizeof(float) * 9 * n, s_K);
-    put(b->pts, sizeof(double) * 3 * (size_t)no, s_X);
-    put(b->obs_uv, sizeof(float) * 2 * (size_t)no, s_uv);
-    char* d = ctx->pose_buf;
-    HIP_OK(hipMemcpyAsync(d, h.data(), in_b, hipMemcpyHostToDevice, ctx->stream));
-    const int* d_off = reinterpret_cast<const int*>(d);
-    const double* d_cam = reinterpret_cast<const double*>(d + s_off);
-    const float* d_K = reinterpret_cast<const float*>(d + s_off + s_cam);
-    const double* d_X = reinterpret_cast<const double*>(d + s_off + s_cam + s_K);
-    const float2* d_uv = reinterpret_cast<const float2*>(d + s_off + s_cam + s_K + s_X);
-    double* d_out = reinterpret_cast<double*>(d + in_b);
-    double* d_sum = reinterpret_cast<double*>(d + in_b + s_cam);
-    launch_pose_batch(n, d_off, d_cam, d_K, d_X, d_uv, b->huber_a, po, d_out, d_sum, ctx->stream);
+    SectionLayout L(16);
+    const size_t o_off = L.add(sizeof(int) * (N + 1)), o_cam = L.add(sizeof(double) * 6 * N),
+                 o_K = L.add(sizeof(float) * 9 * N), o_X = L.add(sizeof(double) * 3 * NO),
+                 o_uv = L.add(sizeof(float) * 2 * NO);
+    L.end_inputs();
+    const size_t o_out = L.add(sizeof(double) * 6 * N), o_sum = L.add(sizeof(double) * 8 * N);
+    L.end_outputs();
+    ctx->pose.reserve(ctx, L.total, fn);
+    std::vector<char>& h = ctx->pose.host;
+    h.assign(L.total, 0);
+    stage(h, o_off, b->obs_offset, sizeof(int) * (N + 1));
+    stage(h, o_cam, b->cams, sizeof(double) * 6 * N);
+    stage(h, o_K, b->K, sizeof(float) * 9 * N);
+    stage(h, o_X, b->pts, sizeof(double) * 3 * NO);
+    stage(h, o_uv, b->obs_uv, sizeof(float) * 2 * NO);
+    char* d = ctx->pose.dev;
+    HIP_OK(hipMemcpyAsync(d, h.data(), L.in_b, hipMemcpyHostToDevice, ctx->stream));
+    launch_pose_batch(n, at<const int>(d, o_off), at<const double>(d, o_cam), at<const float>(d, o_K),
+                      at<const double>(d, o_X), at<const float2>(d, o_uv), b->huber_a, po, at<double>(d, o_out),
+                      at<double>(d, o_sum), ctx->stream);
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(h.data() + in_b, d + in_b, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipMemcpyAsync(h.data() + L.in_b, d + L.in_b, L.io_b - L.in_b, hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(cams_out, h.data() + in_b, sizeof(double) * 6 * n);
+    std::memcpy(cams_out, h.data() + o_out, sizeof(double) * 6 * N);
     if (summaries) {
-      const double* sm = reinterpret_cast<const double*>(h.data() + in_b + s_cam);
       const double wall = now_s() - t0;
-      for (int i = 0; i < n; ++i) {
-        ba_summary S{};
-        S.initial_cost = sm[8 * i];
-        S.final_cost = sm[8 * i + 1];
-        S.num_iterations = (int)sm[8 * i + 2];
-        S.num_successful_steps = (int)sm[8 * i + 3];
-        S.num_unsuccessful_steps = (int)sm[8 * i + 4];
-        S.termination_type = (int)sm[8 * i + 5];
-        S.total_time_s = wall;
-        summaries[i] = S;
-      }
+      for (size_t i = 0; i < N; ++i) summaries[i] = unpack_summary(at<const double>(h.data(), o_sum) + 8 * i, wall, false);
     }
   });
 }
 
 // ---------------------------------------------------------------------------
-// ba_solve_window_batch: host side.  Per problem: validate, find the variable
-// observed cameras (compact columns in increasing camera index) and the
-// variable points, sort the observations by (point, camera) as set_problem
-// does, build the point CSR, the (point, camera) group heads and the camera
-// CSR; one upload, one launch (ba_window.hip), one download.
+// ba_solve_window_batch: host side.  The structure of every problem
+// (pack_window_structure, host/ba_batch_pack.hpp), one upload, one launch
+// (ba_window.hip), one download.
 // ---------------------------------------------------------------------------
 int ba_solve_window_batch(ba_ctx* ctx, const ba_window_batch* b, const ba_options* opt, double* cams_out,
                           double* pts_out, ba_summary* summaries) {
@@ -2350,201 +2354,99 @@ int ba_solve_window_batch(ba_ctx* ctx, const ba_window_batch* b, const ba_option
   return guarded(ctx, [&] {
     const std::string fn = "ba_solve_window_batch: ";
     if (!b || b->n_problems < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "bad batch"};
-    ba_options o;
-    if (opt) o = *opt; else ba_default_options(&o);
+    const ba_options o = options_or_default(opt);
     if (o.linear_solver != BA_DENSE_SCHUR) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "linear_solver must be BA_DENSE_SCHUR"};
     if (o.precision != BA_FP64) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "precision must be BA_FP64"};
-    const int n = b->n_problems;
-    if (n > 0 && (!b->cam_offset || !b->pt_offset || !b->obs_offset)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null offset array"};
-    if (n > 0 && (b->cam_offset[0] != 0 || b->pt_offset[0] != 0 || b->obs_offset[0] != 0))
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "offset[0] != 0"};
-    for (int i = 0; i < n; ++i)
-      if (b->cam_offset[i + 1] < b->cam_offset[i] || b->pt_offset[i + 1] < b->pt_offset[i] ||
-          b->obs_offset[i + 1] < b->obs_offset[i])
-        throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "an offset array decreases at problem " + std::to_string(i)};
-    const size_t NC = n ? b->cam_offset[n] : 0, NP = n ? b->pt_offset[n] : 0, NO = n ? b->obs_offset[n] : 0;
-    if ((NC && (!b->cams || !b->K || !cams_out)) || (NP && (!b->pts || !pts_out)) ||
-        (NO && (!b->obs_cam || !b->obs_pt || !b->obs_uv)))
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null array"};
     const double t0 = now_s();
-    // ---- structure
-    std::vector<WinProb> prob(n);
-    std::vector<int> cam_vc(NC, -1), pt_off(NP + n, 0), obs_cam(NO), obs_slot(NO, -1), cam_off, cam_obs;
-    std::vector<uint8_t> pt_var(NP, 0);
-    std::vector<float> uv(2 * NO);
-    std::vector<int> order, cnt;
-    size_t NV = 0, lds = 0;
-    cam_obs.reserve(NO);
-    for (int i = 0; i < n; ++i) {
-      WinProb& q = prob[i];
-      q = WinProb{};
-      q.cam0 = b->cam_offset[i]; q.pt0 = b->pt_offset[i]; q.obs0 = b->obs_offset[i];
-      q.nc = b->cam_offset[i + 1] - q.cam0; q.np = b->pt_offset[i + 1] - q.pt0; q.no = b->obs_offset[i + 1] - q.obs0;
-      const int32_t* oc = b->obs_cam + q.obs0;
-      const int32_t* op = b->obs_pt + q.obs0;
-      for (int k = 0; k < q.no; ++k)
-        if (oc[k] < 0 || oc[k] >= q.nc || op[k] < 0 || op[k] >= q.np)
-          throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "problem " + std::to_string(i) + ": observation " +
-                                                     std::to_string(k) + " has a local index out of range"};
-      auto cfix = [&](int c) { return b->cam_fixed && b->cam_fixed[q.cam0 + c]; };
-      auto pfix = [&](int p) { return b->pt_fixed && b->pt_fixed[q.pt0 + p]; };
-      // variable blocks that some residual touches
-      int* vc = cam_vc.data() + q.cam0;
-      for (int k = 0; k < q.no; ++k) {
-        if (!cfix(oc[k])) vc[oc[k]] = 0;
-        if (!pfix(op[k])) pt_var[q.pt0 + op[k]] = 1;
-      }
-      int nvc = 0;
-      for (int c = 0; c < q.nc; ++c) if (vc[c] == 0) vc[c] = nvc++;
-      if (nvc > BA_WINDOW_MAX_CAMS)
-        throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "problem " + std::to_string(i) + " has " + std::to_string(nvc) +
-                                                   " variable observed cameras (at most " +
-                                                   std::to_string(BA_WINDOW_MAX_CAMS) + ")"};
-      q.nvc = nvc;
-      q.vc0 = (int)NV;
-      NV += nvc;
-      lds = std::max(lds, window_lds_bytes(nvc));
-      // observations by (point, camera), stable
-      order.resize(q.no);
-      for (int k = 0; k < q.no; ++k) order[k] = k;
-      std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-        return op[x] != op[y] ? op[x] < op[y] : oc[x] < oc[y];
-      });
-      q.poff0 = q.pt0 + i;
-      int* po = pt_off.data() + q.poff0;
-      for (int k = 0; k < q.no; ++k) po[op[k] + 1]++;
-      for (int p = 0; p < q.np; ++p) po[p + 1] += po[p];
-      q.coff0 = (int)cam_off.size();
-      q.vobs0 = (int)cam_obs.size();
-      cnt.assign(nvc + 1, 0);
-      for (int k = 0; k < q.no; ++k) {
-        const int src = order[k], c = oc[src], p = op[src];
-        obs_cam[q.obs0 + k] = c;
-        uv[2 * ((size_t)q.obs0 + k)] = b->obs_uv[2 * ((size_t)q.obs0 + src)];
-        uv[2 * ((size_t)q.obs0 + k) + 1] = b->obs_uv[2 * ((size_t)q.obs0 + src) + 1];
-        if (vc[c] >= 0) {
-          cnt[vc[c] + 1]++;
-          const bool head = k == 0 || op[order[k - 1]] != p || oc[order[k - 1]] != c;
-          if (head && pt_var[q.pt0 + p]) obs_slot[q.obs0 + k] = vc[c];
-        }
-      }
-      for (int v = 0; v < nvc; ++v) cnt[v + 1] += cnt[v];
-      cam_off.insert(cam_off.end(), cnt.begin(), cnt.end());
-      cam_obs.resize(q.vobs0 + cnt[nvc]);
-      for (int k = 0; k < q.no; ++k) {
-        const int v = vc[obs_cam[q.obs0 + k]];
-        if (v >= 0) cam_obs[q.vobs0 + cnt[v]++] = k;
-      }
-    }
+    const WindowPack w = pack_window_structure(*b);
+    const int n = b->n_problems;
+    const size_t NC = w.cam_vc.size(), NP = w.pt_var.size(), NO = w.obs_cam.size(), NV = w.NV;
+    if ((NC && (!b->cams || !b->K || !cams_out)) || (NP && (!b->pts || !pts_out)))
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null array"};
     if (n == 0) {
       ctx->win_log.clear();
       ctx->win_log_n.clear();
       return;
     }
+    // the launch's dynamic LDS: the largest over the problems (not monotone in nvc)
+    size_t lds = 0;
+    for (const WinProb& q : w.prob) lds = std::max(lds, window_lds_bytes(q.nvc));
     // ---- one buffer: inputs (uploaded) | outputs (downloaded) | scratch
     const size_t log_cap = (size_t)std::max(o.max_num_iterations, 0) + 1;
     if (log_cap > (size_t(1) << 40) / (sizeof(ba_iteration) * (size_t)n))
       throw BaError{BA_ERR_OUT_OF_MEMORY, fn + "the iteration logs do not fit (max_num_iterations x n_problems)"};
-    auto al =[](size_t x) { return (x + 255) & ~size_t(255); };
-    size_t at = 0;
-    auto sec = [&](size_t bytes) { const size_t r = at; at += al(bytes); return r; };
-    const size_t o_prob = sec(sizeof(WinProb) * n), o_cams = sec(sizeof(double) * 6 * NC), o_pts = sec(sizeof(double) * 3 * NP),
-                 o_K = sec(sizeof(float) * 9 * NC), o_extr = sec(sizeof(float) * 16 * NC), o_vc = sec(sizeof(int) * NC),
-                 o_pv = sec(NP), o_poff = sec(sizeof(int) * (NP + n)), o_oc = sec(sizeof(int) * NO),
-                 o_slot = sec(sizeof(int) * NO), o_uv = sec(sizeof(float) * 2 * NO),
-                 o_coff = sec(sizeof(int) * cam_off.size()), o_cobs = sec(sizeof(int) * cam_obs.size());
-    const size_t in_b = at;
-    const size_t o_co = sec(sizeof(double) * 6 * NC), o_po = sec(sizeof(double) * 3 * NP), o_sum = sec(sizeof(double) * 8 * n),
-                 o_log = sec(sizeof(ba_iteration) * log_cap * n);
-    const size_t io_b = at;
-    const size_t w_pts = sec(sizeof(double) * 6 * NP), w_ctab = sec(sizeof(double) * 2 * kWinTbl * NC),
-                 w_vrec = sec(sizeof(double) * kWinVRec * NC), w_JR = sec(sizeof(double) * 2 * kWinJR * NO),
-                 w_Hp = sec(sizeof(double) * 18 * NP), w_sp = sec(sizeof(double) * 3 * NP),
-                 w_prec = sec(sizeof(double) * 9 * NP), w_W = sec(sizeof(double) * 18 * NO),
-                 w_hc = sec(sizeof(double) * 54 * NV);
-    const size_t total = at;
+    SectionLayout L(256);
+    const size_t o_prob = L.add(sizeof(WinProb) * n), o_cams = L.add(sizeof(double) * 6 * NC),
+                 o_pts = L.add(sizeof(double) * 3 * NP), o_K = L.add(sizeof(float) * 9 * NC),
+                 o_extr = L.add(sizeof(float) * 16 * NC), o_vc = L.add(sizeof(int) * NC), o_pv = L.add(NP),
+                 o_poff = L.add(sizeof(int) * (NP + n)), o_oc = L.add(sizeof(int) * NO),
+                 o_slot = L.add(sizeof(int) * NO), o_uv = L.add(sizeof(float) * 2 * NO),
+                 o_coff = L.add(sizeof(int) * w.cam_off.size()), o_cobs = L.add(sizeof(int) * w.cam_obs.size());
+    L.end_inputs();
+    const size_t o_co = L.add(sizeof(double) * 6 * NC), o_po = L.add(sizeof(double) * 3 * NP),
+                 o_sum = L.add(sizeof(double) * 8 * n), o_log = L.add(sizeof(ba_iteration) * log_cap * n);
+    L.end_outputs();
+    const size_t w_pts = L.add(sizeof(double) * 6 * NP), w_ctab = L.add(sizeof(double) * 2 * kWinTbl * NC),
+                 w_vrec = L.add(sizeof(double) * kWinVRec * NC), w_JR = L.add(sizeof(double) * 2 * kWinJR * NO),
+                 w_Hp = L.add(sizeof(double) * 18 * NP), w_sp = L.add(sizeof(double) * 3 * NP),
+                 w_prec = L.add(sizeof(double) * 9 * NP), w_W = L.add(sizeof(double) * 18 * NO),
+                 w_hc = L.add(sizeof(double) * 54 * NV);
     HIP_OK(hipSetDevice(ctx->device));
-    if (total > ctx->win_cap) {
-      if (ctx->win_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->win_buf); }
-      ctx->win_buf = nullptr;
-      ctx->win_cap = 0;
-      const hipError_t e = hipMalloc(&ctx->win_buf, total);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();   // (not sticky: the context stays usable)
-        ctx->win_buf = nullptr;
-        throw BaError{e == hipErrorOutOfMemory ? BA_ERR_OUT_OF_MEMORY : BA_ERR_DEVICE,
-                      fn + "scratch of " + std::to_string(total) + " bytes: " + hipGetErrorString(e)};
-      }
-      ctx->win_cap = total;
-    }
-    std::vector<char>& h = ctx->win_host;
-    h.resize(io_b);
-    auto put = [&](size_t off, const void* src, size_t nb) { if (nb) std::memcpy(h.data() + off, src, nb); };
-    put(o_prob, prob.data(), sizeof(WinProb) * n);
-    put(o_cams, b->cams, sizeof(double) * 6 * NC);
-    put(o_pts, b->pts, sizeof(double) * 3 * NP);
-    put(o_K, b->K, sizeof(float) * 9 * NC);
-    if (b->cam_fixed_extr) put(o_extr, b->cam_fixed_extr, sizeof(float) * 16 * NC);
+    ctx->win.reserve(ctx, L.total, fn);
+    std::vector<char>& h = ctx->win.host;
+    h.resize(L.io_b);
+    stage(h, o_prob, w.prob.data(), sizeof(WinProb) * n);
+    stage(h, o_cams, b->cams, sizeof(double) * 6 * NC);
+    stage(h, o_pts, b->pts, sizeof(double) * 3 * NP);
+    stage(h, o_K, b->K, sizeof(float) * 9 * NC);
+    if (b->cam_fixed_extr) stage(h, o_extr, b->cam_fixed_extr, sizeof(float) * 16 * NC);
     else std::memset(h.data() + o_extr, 0, sizeof(float) * 16 * NC);
-    put(o_vc, cam_vc.data(), sizeof(int) * NC);
-    put(o_pv, pt_var.data(), NP);
-    put(o_poff, pt_off.data(), sizeof(int) * (NP + n));
-    put(o_oc, obs_cam.data(), sizeof(int) * NO);
-    put(o_slot, obs_slot.data(), sizeof(int) * NO);
-    put(o_uv, uv.data(), sizeof(float) * 2 * NO);
-    put(o_coff, cam_off.data(), sizeof(int) * cam_off.size());
-    put(o_cobs, cam_obs.data(), sizeof(int) * cam_obs.size());
-    char* d = ctx->win_buf;
-    HIP_OK(hipMemcpyAsync(d, h.data(), in_b, hipMemcpyHostToDevice, ctx->stream));
+    stage(h, o_vc, w.cam_vc.data(), sizeof(int) * NC);
+    stage(h, o_pv, w.pt_var.data(), NP);
+    stage(h, o_poff, w.pt_off.data(), sizeof(int) * (NP + n));
+    stage(h, o_oc, w.obs_cam.data(), sizeof(int) * NO);
+    stage(h, o_slot, w.obs_slot.data(), sizeof(int) * NO);
+    stage(h, o_uv, w.uv.data(), sizeof(float) * 2 * NO);
+    stage(h, o_coff, w.cam_off.data(), sizeof(int) * w.cam_off.size());
+    stage(h, o_cobs, w.cam_obs.data(), sizeof(int) * w.cam_obs.size());
+    char* d = ctx->win.dev;
+    HIP_OK(hipMemcpyAsync(d, h.data(), L.in_b, hipMemcpyHostToDevice, ctx->stream));
     WinArgs A{};
-    A.prob = reinterpret_cast<const WinProb*>(d + o_prob);
+    A.prob = at<const WinProb>(d, o_prob);
     A.NC = NC; A.NP = NP; A.NO = NO; A.NV = NV;
     A.log_cap = (int)std::min<size_t>(log_cap, 0x7fffffff);
     A.huber_a = b->huber_a;
-    auto dd = [&](size_t off) { return reinterpret_cast<double*>(d + off); };
-    auto di = [&](size_t off) { return reinterpret_cast<const int*>(d + off); };
-    A.cams_in = dd(o_cams); A.pts_in = dd(o_pts);
-    A.K = reinterpret_cast<const float*>(d + o_K); A.extr = reinterpret_cast<const float*>(d + o_extr);
-    A.cam_vc = di(o_vc); A.pt_var = reinterpret_cast<const uint8_t*>(d + o_pv);
-    A.pt_off = di(o_poff); A.obs_cam = di(o_oc); A.obs_slot = di(o_slot);
-    A.uv = reinterpret_cast<const float2*>(d + o_uv);
-    A.cam_off = di(o_coff); A.cam_obs = di(o_cobs);
-    A.pts = dd(w_pts); A.ctab = dd(w_ctab); A.vrec = dd(w_vrec); A.JR = dd(w_JR); A.Hp = dd(w_Hp);
-    A.scale_p = dd(w_sp); A.prec = dd(w_prec); A.Wb = dd(w_W); A.hc = dd(w_hc);
-    A.cams_out = dd(o_co); A.pts_out = dd(o_po); A.summ = dd(o_sum); A.log = d + o_log;
-    PoseOpts po{o.max_num_iterations, o.max_num_consecutive_invalid_steps, o.jacobi_scaling,
-                o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance, o.initial_trust_region_radius,
-                o.max_trust_region_radius, o.min_trust_region_radius, o.min_relative_decrease, o.min_lm_diagonal,
-                o.max_lm_diagonal};
+    A.cams_in = at<double>(d, o_cams); A.pts_in = at<double>(d, o_pts);
+    A.K = at<const float>(d, o_K); A.extr = at<const float>(d, o_extr);
+    A.cam_vc = at<const int>(d, o_vc); A.pt_var = at<const uint8_t>(d, o_pv);
+    A.pt_off = at<const int>(d, o_poff); A.obs_cam = at<const int>(d, o_oc); A.obs_slot = at<const int>(d, o_slot);
+    A.uv = at<const float2>(d, o_uv);
+    A.cam_off = at<const int>(d, o_coff); A.cam_obs = at<const int>(d, o_cobs);
+    A.pts = at<double>(d, w_pts); A.ctab = at<double>(d, w_ctab); A.vrec = at<double>(d, w_vrec);
+    A.JR = at<double>(d, w_JR); A.Hp = at<double>(d, w_Hp); A.scale_p = at<double>(d, w_sp);
+    A.prec = at<double>(d, w_prec); A.Wb = at<double>(d, w_W); A.hc = at<double>(d, w_hc);
+    A.cams_out = at<double>(d, o_co); A.pts_out = at<double>(d, o_po); A.summ = at<double>(d, o_sum); A.log = d + o_log;
+    const PoseOpts po = pose_opts(o);
     const double t_prep = now_s() - t0;
     HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
     HIP_OK((hipError_t)launch_window_batch(n, A, po, lds, ctx->stream));
     HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
-    HIP_OK(hipMemcpyAsync(h.data() + in_b, d + in_b, io_b - in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipMemcpyAsync(h.data() + L.in_b, d + L.in_b, L.io_b - L.in_b, hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(hipStreamSynchronize(ctx->stream));
     float kernel_ms = 0.0f;
     HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
     if (NC) std::memcpy(cams_out, h.data() + o_co, sizeof(double) * 6 * NC);
     if (NP) std::memcpy(pts_out, h.data() + o_po, sizeof(double) * 3 * NP);
-    const double* sm = reinterpret_cast<const double*>(h.data() + o_sum);
+    const double* sm = at<const double>(h.data(), o_sum);
     ctx->win_log_cap = A.log_cap;
     ctx->win_log_n.resize(n);
-    const ba_iteration* lg = reinterpret_cast<const ba_iteration*>(h.data() + o_log);
+    const ba_iteration* lg = at<const ba_iteration>(h.data(), o_log);
     ctx->win_log.assign(lg, lg + log_cap * n);
     const double wall = now_s() - t0;
     ctx->win_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * wall};
     for (int i = 0; i < n; ++i) {
       ctx->win_log_n[i] = (int)sm[8 * i + 6];
-      if (!summaries) continue;
-      ba_summary S{};
-      S.initial_cost = sm[8 * i];
-      S.final_cost = sm[8 * i + 1];
-      S.num_iterations = (int)sm[8 * i + 2];
-      S.num_successful_steps = (int)sm[8 * i + 3];
-      S.num_unsuccessful_steps = (int)sm[8 * i + 4];
-      S.termination_type = (int)sm[8 * i + 5];
-      S.total_time_s = S.linearize_time_s = S.solve_time_s = wall;
-      summaries[i] = S;
+      if (summaries) summaries[i] = unpack_summary(sm + 8 * i, wall, true);
     }
   });
 }
@@ -2559,10 +2461,7 @@ int ba_get_window_iteration_log(ba_ctx* ctx, int problem, ba_iteration* out, int
 }
 
 int ba_window_times(ba_ctx* ctx, double* ms, int n) {
-  if (!ctx) return -BA_ERR_INVALID_ARGUMENT;
-  const int m = (int)ctx->win_ms.size();
-  for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = ctx->win_ms[i];
-  return m;
+  return ctx ? copy_times(ctx->win_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
 }
 
 // ---------------------------------------------------------------------------
@@ -2596,8 +2495,7 @@ int ba_triangulate(ba_ctx* ctx, const ba_tri_batch* b, const ba_tri_options* top
     const int all_checks = BA_TRI_CHECK_CHEIRALITY | BA_TRI_CHECK_CHI2 | BA_TRI_CHECK_SCALE;
     if (t.checks & ~all_checks) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "unknown checks bits " + std::to_string(t.checks)};
     if (t.min_views < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "min_views " + std::to_string(t.min_views) + " is negative"};
-    ba_options o;
-    if (opt) o = *opt; else ba_default_options(&o);
+    ba_options o = options_or_default(opt);
     if (t.refine) {
       if (o.linear_solver != BA_DENSE_SCHUR) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "linear_solver must be BA_DENSE_SCHUR"};
       if (o.precision != BA_FP64) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "precision must be BA_FP64"};
@@ -2606,10 +2504,7 @@ int ba_triangulate(ba_ctx* ctx, const ba_tri_batch* b, const ba_tri_options* top
     if (np == 0) return;
     if (!b->obs_offset) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null obs_offset"};
     if (!pts_out || !status) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    if (b->obs_offset[0] != 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "obs_offset[0] != 0"};
-    for (int p = 0; p < np; ++p)
-      if (b->obs_offset[p + 1] < b->obs_offset[p])
-        throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "obs_offset decreases at point " + std::to_string(p)};
+    check_offsets(fn.c_str(), "obs_offset", b->obs_offset, np, "point");
     const size_t no = (size_t)b->obs_offset[np];
     if (no > 0 && (!b->obs_cam || !b->obs_uv)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null observation array"};
     if (nc > 0 && (!b->extr || !b->K)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null camera array (extr, K)"};
@@ -2625,70 +2520,47 @@ int ba_triangulate(ba_ctx* ctx, const ba_tri_batch* b, const ba_tri_options* top
     const double t0 = now_s();
     const bool given = t.init == BA_TRI_INIT_GIVEN, has_ctr = b->cam_center != nullptr, has_scale = b->obs_scale != nullptr;
     // ---- one buffer: inputs (uploaded) | outputs (downloaded) | scratch
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    size_t at = 0;
-    auto sec = [&](size_t bytes) { const size_t r = at; at += al(bytes); return r; };
-    const size_t o_extr = sec(sizeof(float) * 16 * nc), o_ctr = sec(has_ctr ? sizeof(float) * 3 * nc : 0),
-                 o_K = sec(sizeof(float) * 9 * nc), o_off = sec(sizeof(int) * ((size_t)np + 1)),
-                 o_oc = sec(sizeof(int) * no), o_uv = sec(sizeof(float) * 2 * no),
-                 o_sc = sec(has_scale ? sizeof(float) * no : 0), o_init = sec(given ? sizeof(double) * 3 * np : 0);
-    const size_t in_b = at;
-    const size_t o_pts = sec(sizeof(double) * 3 * np), o_sum = sec(sizeof(double) * 6 * np), o_st = sec((size_t)np);
-    const size_t io_b = at;
-    const size_t w_rec = sec(sizeof(double) * kTriRec * nc);
-    const size_t total = at;
+    SectionLayout L(256);
+    const size_t o_extr = L.add(sizeof(float) * 16 * nc), o_ctr = L.add(has_ctr ? sizeof(float) * 3 * nc : 0),
+                 o_K = L.add(sizeof(float) * 9 * nc), o_off = L.add(sizeof(int) * ((size_t)np + 1)),
+                 o_oc = L.add(sizeof(int) * no), o_uv = L.add(sizeof(float) * 2 * no),
+                 o_sc = L.add(has_scale ? sizeof(float) * no : 0), o_init = L.add(given ? sizeof(double) * 3 * np : 0);
+    L.end_inputs();
+    const size_t o_pts = L.add(sizeof(double) * 3 * np), o_sum = L.add(sizeof(double) * 6 * np), o_st = L.add((size_t)np);
+    L.end_outputs();
+    const size_t w_rec = L.add(sizeof(double) * kTriRec * nc);
     HIP_OK(hipSetDevice(ctx->device));
-    if (total > ctx->tri_cap) {
-      if (ctx->tri_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->tri_buf); }
-      ctx->tri_buf = nullptr;
-      ctx->tri_cap = 0;
-      const hipError_t e = hipMalloc(&ctx->tri_buf, total);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();   // (not sticky: the context stays usable)
-        ctx->tri_buf = nullptr;
-        throw BaError{e == hipErrorOutOfMemory ? BA_ERR_OUT_OF_MEMORY : BA_ERR_DEVICE,
-                      fn + "scratch of " + std::to_string(total) + " bytes: " + hipGetErrorString(e)};
-      }
-      ctx->tri_cap = total;
-    }
-    std::vector<char>& h = ctx->tri_host;
-    h.resize(io_b);
-    auto put = [&](size_t off, const void* src, size_t nb) { if (nb) std::memcpy(h.data() + off, src, nb); };
-    put(o_extr, b->extr, sizeof(float) * 16 * nc);
-    if (has_ctr) put(o_ctr, b->cam_center, sizeof(float) * 3 * nc);
-    put(o_K, b->K, sizeof(float) * 9 * nc);
-    put(o_off, b->obs_offset, sizeof(int) * ((size_t)np + 1));
-    put(o_oc, b->obs_cam, sizeof(int) * no);
-    put(o_uv, b->obs_uv, sizeof(float) * 2 * no);
-    if (has_scale) put(o_sc, b->obs_scale, sizeof(float) * no);
-    if (given) put(o_init, b->pts_init, sizeof(double) * 3 * np);
-    char* d = ctx->tri_buf;
-    HIP_OK(hipMemcpyAsync(d, h.data(), in_b, hipMemcpyHostToDevice, ctx->stream));
+    ctx->tri.reserve(ctx, L.total, fn);
+    std::vector<char>& h = ctx->tri.host;
+    h.resize(L.io_b);
+    stage(h, o_extr, b->extr, sizeof(float) * 16 * nc);
+    if (has_ctr) stage(h, o_ctr, b->cam_center, sizeof(float) * 3 * nc);
+    stage(h, o_K, b->K, sizeof(float) * 9 * nc);
+    stage(h, o_off, b->obs_offset, sizeof(int) * ((size_t)np + 1));
+    stage(h, o_oc, b->obs_cam, sizeof(int) * no);
+    stage(h, o_uv, b->obs_uv, sizeof(float) * 2 * no);
+    if (has_scale) stage(h, o_sc, b->obs_scale, sizeof(float) * no);
+    if (given) stage(h, o_init, b->pts_init, sizeof(double) * 3 * np);
+    char* d = ctx->tri.dev;
+    HIP_OK(hipMemcpyAsync(d, h.data(), L.in_b, hipMemcpyHostToDevice, ctx->stream));
     TriArgs A{};
     A.n_pts = np; A.n_cams = nc;
     A.init_given = given; A.refine = t.refine; A.min_views = t.min_views; A.checks = t.checks;
     A.behind_any = t.behind_rule;
     A.huber_a = b->huber_a;
-    auto df = [&](size_t off) { return reinterpret_cast<const float*>(d + off); };
-    A.extr = df(o_extr); A.center = has_ctr ? df(o_ctr) : nullptr; A.K = df(o_K);
-    A.off = reinterpret_cast<const int*>(d + o_off); A.obs_cam = reinterpret_cast<const int*>(d + o_oc);
-    A.uv = reinterpret_cast<const float2*>(d + o_uv);
-    A.scale = has_scale ? df(o_sc) : nullptr;
-    A.pts_init = given ? reinterpret_cast<const double*>(d + o_init) : nullptr;
-    A.rec = reinterpret_cast<double*>(d + w_rec);
-    A.pts_out = reinterpret_cast<double*>(d + o_pts);
-    A.summ = reinterpret_cast<double*>(d + o_sum);
-    A.status = reinterpret_cast<uint8_t*>(d + o_st);
-    PoseOpts po{o.max_num_iterations, o.max_num_consecutive_invalid_steps, o.jacobi_scaling,
-                o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance, o.initial_trust_region_radius,
-                o.max_trust_region_radius, o.min_trust_region_radius, o.min_relative_decrease, o.min_lm_diagonal,
-                o.max_lm_diagonal};
+    A.extr = at<const float>(d, o_extr); A.center = has_ctr ? at<const float>(d, o_ctr) : nullptr; A.K = at<const float>(d, o_K);
+    A.off = at<const int>(d, o_off); A.obs_cam = at<const int>(d, o_oc); A.uv = at<const float2>(d, o_uv);
+    A.scale = has_scale ? at<const float>(d, o_sc) : nullptr;
+    A.pts_init = given ? at<const double>(d, o_init) : nullptr;
+    A.rec = at<double>(d, w_rec);
+    A.pts_out = at<double>(d, o_pts); A.summ = at<double>(d, o_sum); A.status = at<uint8_t>(d, o_st);
+    const PoseOpts po = pose_opts(o);
     const double t_prep = now_s() - t0;
     HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
     launch_triangulate(A, po, ctx->stream);
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
-    HIP_OK(hipMemcpyAsync(h.data() + in_b, d + in_b, io_b - in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipMemcpyAsync(h.data() + L.in_b, d + L.in_b, L.io_b - L.in_b, hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(hipStreamSynchronize(ctx->stream));
     float kernel_ms = 0.0f;
     HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
@@ -2696,28 +2568,14 @@ int ba_triangulate(ba_ctx* ctx, const ba_tri_batch* b, const ba_tri_options* top
     std::memcpy(status, h.data() + o_st, (size_t)np);
     const double wall = now_s() - t0;
     ctx->tri_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * wall};
-    if (summaries) {
-      const double* sm = reinterpret_cast<const double*>(h.data() + o_sum);
-      for (int i = 0; i < np; ++i) {
-        ba_summary S{};
-        S.initial_cost = sm[6 * (size_t)i];
-        S.final_cost = sm[6 * (size_t)i + 1];
-        S.num_iterations = (int)sm[6 * (size_t)i + 2];
-        S.num_successful_steps = (int)sm[6 * (size_t)i + 3];
-        S.num_unsuccessful_steps = (int)sm[6 * (size_t)i + 4];
-        S.termination_type = (int)sm[6 * (size_t)i + 5];
-        S.total_time_s = S.linearize_time_s = S.solve_time_s = wall;
-        summaries[i] = S;
-      }
-    }
+    if (summaries)
+      for (size_t i = 0; i < (size_t)np; ++i)
+        summaries[i] = unpack_summary(at<const double>(h.data(), o_sum) + 6 * i, wall, true);
   });
 }
 
 int ba_triangulate_times(ba_ctx* ctx, double* ms, int n) {
-  if (!ctx) return -BA_ERR_INVALID_ARGUMENT;
-  const int m = (int)ctx->tri_ms.size();
-  for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = ctx->tri_ms[i];
-  return m;
+  return ctx ? copy_times(ctx->tri_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
 }
 
 int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double* Hcc, double* gc, double* S,
@@ -2726,8 +2584,7 @@ int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double*
   return guarded(ctx, [&] {
     if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, "no problem"};
     HIP_OK(hipSetDevice(ctx->device));
-    ba_options o;
-    ba_default_options(&o);   // DENSE_SCHUR, fp64
+    ba_options o = options_or_default(nullptr);   // DENSE_SCHUR, fp64
     ctx->read_env();
     // iteration 0's linearisation (Jacobi scaling from it), then the step's
     // reduced system without its factorisation
@@ -2817,10 +2674,7 @@ int ba_covariance_iterative_bench(ba_ctx* ctx, int cols, int reps, int warmup, d
 }
 
 int ba_covariance_times(ba_ctx* ctx, double* ms, int n) {
-  if (!ctx) return -BA_ERR_INVALID_ARGUMENT;
-  const int m = (int)ctx->cov_ms.size();
-  for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = ctx->cov_ms[i];
-  return m;
+  return ctx ? copy_times(ctx->cov_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
 }
 
 int ba_synchronize(ba_ctx* ctx) {
@@ -2829,10 +2683,7 @@ int ba_synchronize(ba_ctx* ctx) {
 }
 
 int ba_bench_iteration_times(ba_ctx* ctx, double* ms, int n) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  const int m = (int)ctx->bench_ms.size();
-  for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = ctx->bench_ms[i];
-  return m;
+  return ctx ? copy_times(ctx->bench_ms, ms, n) : BA_ERR_INVALID_ARGUMENT;   // (positive, unlike the other getters)
 }
 
 int ba_stream_copy(ba_ctx* ctx, size_t bytes, int reps, double* gbs) {
@@ -2842,14 +2693,9 @@ int ba_stream_copy(ba_ctx* ctx, size_t bytes, int reps, double* gbs) {
     const size_t n2 = bytes / 16;
     double *a = nullptr, *b = nullptr;
     HIP_OK(hipMalloc(&a, n2 * 16));
-    if (hipMalloc(&b, n2 * 16) != hipSuccess) {
-      (void)hipFree(a);
-      throw BaError{BA_ERR_OUT_OF_MEMORY, "ba_stream_copy: hipMalloc"};
-    }
-    struct Free {
-      double *a, *b;
-      ~Free() { (void)hipFree(a); (void)hipFree(b); }
-    } fr{a, b};
+    DevFree free_a{a};
+    if (hipMalloc(&b, n2 * 16) != hipSuccess) throw BaError{BA_ERR_OUT_OF_MEMORY, "ba_stream_copy: hipMalloc"};
+    DevFree free_b{b};
     HIP_OK(hipMemsetAsync(a, 0, n2 * 16, ctx->stream));
     bahip::launch_stream_copy(a, b, n2, ctx->stream);   // warm-up
     HIP_OK(hipGetLastError());
@@ -2869,8 +2715,7 @@ int ba_bench_iterations(ba_ctx* ctx, const ba_options* opt, int iters, double ra
   return guarded(ctx, [&] {
     if (!ctx->have_problem) throw BaError{BA_ERR_NO_PROBLEM, "no problem"};
     HIP_OK(hipSetDevice(ctx->device));
-    ba_options o;
-    if (opt) o = *opt; else ba_default_options(&o);
+    ba_options o = options_or_default(opt);
     check_options(o);
     ctx->clear_pending();
     if (!ctx->scale_valid) linearize(ctx, true, o.min_lm_diagonal, o.max_lm_diagonal);

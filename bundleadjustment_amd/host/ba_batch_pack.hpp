@@ -1,0 +1,160 @@
+// ba_batch_pack.hpp — host-only packing shared by the batch entry points of
+// ba_solver.hip: the error type, the section layout of a staging buffer, the
+// CSR-offset validation, the summary record, and the structure build of
+// ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
+// plain C++17 without a HIP header and runs under ASan + UBSan
+// (tests/cpp/batch_pack.cpp, `make -C tests/cpp sanitize`).
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/ba_hip.h"
+
+namespace bahip {
+
+struct BaError { int code; std::string msg; };
+
+// Offsets of the sections of one staging buffer, each rounded up to `align`
+// bytes (a power of two): inputs (uploaded) | outputs (downloaded) | scratch.
+struct SectionLayout {
+  explicit SectionLayout(size_t align) : mask(align - 1) {}
+  size_t add(size_t bytes) { const size_t off = total; total += (bytes + mask) & ~mask; return off; }
+  void end_inputs() { in_b = total; }
+  void end_outputs() { io_b = total; }
+  const size_t mask;
+  size_t in_b = 0, io_b = 0, total = 0;   // end of the inputs, of inputs + outputs, of everything
+};
+
+// off[0 .. n] is a CSR offset array: starts at 0 and never decreases
+inline void check_offsets(const char* fn, const char* name, const int32_t* off, int n, const char* unit = "problem") {
+  if (off[0] != 0) throw BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + name + "[0] != 0"};
+  for (int i = 0; i < n; ++i)
+    if (off[i + 1] < off[i])
+      throw BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + name + " decreases at " + unit + " " + std::to_string(i)};
+}
+
+// The device summary record (initial cost, final cost, iterations, successful, unsuccessful,
+// termination, ...) as a ba_summary; split_times: the call's wall time in all three time fields.
+inline ba_summary unpack_summary(const double* rec, double wall, bool split_times) {
+  ba_summary S{};
+  S.initial_cost = rec[0]; S.final_cost = rec[1];
+  S.num_iterations = (int)rec[2]; S.num_successful_steps = (int)rec[3]; S.num_unsuccessful_steps = (int)rec[4];
+  S.termination_type = (int)rec[5];
+  S.total_time_s = wall;
+  if (split_times) S.linearize_time_s = S.solve_time_s = wall;
+  return S;
+}
+
+// One problem of ba_solve_window_batch as the kernel (ba_window.hip) reads it
+struct WinProb {
+  int cam0, pt0, obs0;             // first camera / point / observation of the problem in the concatenated arrays
+  int nc, np, no, nvc;
+  int vc0;                         // first compact variable camera (sum of nvc of the problems before)
+  int poff0;                       // pt_off + poff0: [np + 1] CSR of the observations by point
+  int coff0;                       // cam_off + coff0: [nvc + 1] CSR of cam_obs by compact variable camera
+  int vobs0;                       // cam_obs + vobs0: observations of variable cameras, grouped by camera
+  int pad;
+};
+
+// The structure of a window batch: the index arrays of WinArgs (ba_kernels.h documents them)
+struct WindowPack {
+  std::vector<WinProb> prob;
+  std::vector<int> cam_vc, pt_off, obs_cam, obs_slot, cam_off, cam_obs;
+  std::vector<uint8_t> pt_var;
+  std::vector<float> uv;
+  size_t NV = 0;                   // compact variable cameras of the whole batch
+};
+
+// Per problem: validate, find the variable observed cameras (compact columns
+// in increasing camera index) and the variable points, sort the observations
+// by (point, camera) as set_problem does (stable), build the point CSR, the
+// (point, camera) group heads and the camera CSR.
+// (static: as weak symbols of the shared library the sort's instantiations make the build 4 % slower)
+static inline WindowPack pack_window_structure(const ba_window_batch& b) {
+  const char* const fn = "ba_solve_window_batch: ";   // (a std::string only where an error is raised)
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, fn + what}; };
+  const int n = b.n_problems;
+  if (n < 0) throw invalid("bad batch");
+  if (n == 0) return WindowPack{};
+  if (!b.cam_offset || !b.pt_offset || !b.obs_offset) throw invalid("null offset array");
+  check_offsets(fn, "cam_offset", b.cam_offset, n);
+  check_offsets(fn, "pt_offset", b.pt_offset, n);
+  check_offsets(fn, "obs_offset", b.obs_offset, n);
+  const size_t NC = b.cam_offset[n], NP = b.pt_offset[n], NO = b.obs_offset[n];
+  if (NO && (!b.obs_cam || !b.obs_pt || !b.obs_uv)) throw invalid("null array");
+  std::vector<WinProb> prob(n);
+  std::vector<int> cam_vc(NC, -1), pt_off(NP + n, 0), obs_cam(NO), obs_slot(NO, -1), cam_off, cam_obs;
+  std::vector<uint8_t> pt_var(NP, 0);
+  std::vector<float> uv(2 * NO);
+  std::vector<int> order, cnt;
+  size_t NV = 0;
+  cam_obs.reserve(NO);
+  for (int i = 0; i < n; ++i) {
+    WinProb& q = prob[i];
+    q = WinProb{};
+    q.cam0 = b.cam_offset[i]; q.pt0 = b.pt_offset[i]; q.obs0 = b.obs_offset[i];
+    q.nc = b.cam_offset[i + 1] - q.cam0; q.np = b.pt_offset[i + 1] - q.pt0; q.no = b.obs_offset[i + 1] - q.obs0;
+    const int32_t* oc = b.obs_cam + q.obs0;
+    const int32_t* op = b.obs_pt + q.obs0;
+    for (int k = 0; k < q.no; ++k)
+      if (oc[k] < 0 || oc[k] >= q.nc || op[k] < 0 || op[k] >= q.np)
+        throw invalid("problem " + std::to_string(i) + ": observation " + std::to_string(k) +
+                      " has a local index out of range");
+    auto cfix = [&](int c) { return b.cam_fixed && b.cam_fixed[q.cam0 + c]; };
+    auto pfix = [&](int p) { return b.pt_fixed && b.pt_fixed[q.pt0 + p]; };
+    // variable blocks that some residual touches
+    int* vc = cam_vc.data() + q.cam0;
+    for (int k = 0; k < q.no; ++k) {
+      if (!cfix(oc[k])) vc[oc[k]] = 0;
+      if (!pfix(op[k])) pt_var[q.pt0 + op[k]] = 1;
+    }
+    int nvc = 0;
+    for (int c = 0; c < q.nc; ++c) if (vc[c] == 0) vc[c] = nvc++;
+    if (nvc > BA_WINDOW_MAX_CAMS)
+      throw invalid("problem " + std::to_string(i) + " has " + std::to_string(nvc) +
+                    " variable observed cameras (at most " + std::to_string(BA_WINDOW_MAX_CAMS) + ")");
+    q.nvc = nvc;
+    q.vc0 = (int)NV;
+    NV += nvc;
+    // observations by (point, camera), stable
+    order.resize(q.no);
+    for (int k = 0; k < q.no; ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+      return op[x] != op[y] ? op[x] < op[y] : oc[x] < oc[y];
+    });
+    q.poff0 = q.pt0 + i;
+    int* po = pt_off.data() + q.poff0;
+    for (int k = 0; k < q.no; ++k) po[op[k] + 1]++;
+    for (int p = 0; p < q.np; ++p) po[p + 1] += po[p];
+    q.coff0 = (int)cam_off.size();
+    q.vobs0 = (int)cam_obs.size();
+    cnt.assign(nvc + 1, 0);
+    for (int k = 0; k < q.no; ++k) {
+      const int src = order[k], c = oc[src], p = op[src];
+      obs_cam[q.obs0 + k] = c;
+      uv[2 * ((size_t)q.obs0 + k)] = b.obs_uv[2 * ((size_t)q.obs0 + src)];
+      uv[2 * ((size_t)q.obs0 + k) + 1] = b.obs_uv[2 * ((size_t)q.obs0 + src) + 1];
+      if (vc[c] >= 0) {
+        cnt[vc[c] + 1]++;
+        const bool head = k == 0 || op[order[k - 1]] != p || oc[order[k - 1]] != c;
+        if (head && pt_var[q.pt0 + p]) obs_slot[q.obs0 + k] = vc[c];
+      }
+    }
+    for (int v = 0; v < nvc; ++v) cnt[v + 1] += cnt[v];
+    cam_off.insert(cam_off.end(), cnt.begin(), cnt.end());
+    cam_obs.resize(q.vobs0 + cnt[nvc]);
+    for (int k = 0; k < q.no; ++k) {
+      const int v = vc[obs_cam[q.obs0 + k]];
+      if (v >= 0) cam_obs[q.vobs0 + cnt[v]++] = k;
+    }
+  }
+  return WindowPack{std::move(prob),    std::move(cam_vc),  std::move(pt_off), std::move(obs_cam), std::move(obs_slot),
+                    std::move(cam_off), std::move(cam_obs), std::move(pt_var), std::move(uv),      NV};
+}
+
+}  // namespace bahip

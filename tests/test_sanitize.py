@@ -8,7 +8,10 @@
     and motion-only outer loops, with the oracle (oracle/ba_oracle.cpp,
     compiled into the driver) as the backend: no GPU;
   * io_rt_san — the problem-I/O header (host/ba_io.hpp): BAS load / save and
-    the BAL text reader.
+    the BAL text reader;
+  * batch_pack_san — the host-only packer of the batch entry points
+    (host/ba_batch_pack.hpp): the structure build of ba_solve_window_batch on
+    well-formed and malformed batches, the section layout, check_offsets.
 Each must run clean (exit 0, no sanitizer report, leak check on) and produce
 the same result as the plain build.  GPU code cannot be sanitized on this
 pool; the device side is covered by the parity tests.
@@ -37,10 +40,10 @@ def san_build():
     return CPP
 
 
-def run_clean(cmd):
+def run_clean(cmd, rc=0):
     out = subprocess.run([str(c) for c in cmd], capture_output=True, text=True, timeout=900, env=ENV)
     report = [m for m in MARKERS if m in out.stderr]
-    assert out.returncode == 0 and not report, f"rc={out.returncode} {report}\n{out.stderr[-4000:]}"
+    assert out.returncode == rc and not report, f"rc={out.returncode} {report}\n{out.stderr[-4000:]}"
     return out.stdout
 
 
@@ -71,3 +74,151 @@ def test_problem_io_under_asan_ubsan(san_build, tmp_path):
     bp_py = bio.read_bal(tmp_path / "s.txt", huber_a=2.0)
     bp_cpp = bio.load_problem(tmp_path / "s.bas")
     assert bp_cpp.n_obs == bp_py.n_obs and np.array_equal(bp_cpp.obs_uv, bp_py.obs_uv)
+
+
+# ---------------------------------------------------------------------------
+# the packer of the batch entry points
+# ---------------------------------------------------------------------------
+def pack_batch():
+    """test_window_pack_cpu's ragged batch, then: no observation; every camera
+    constant; duplicated (camera, point) observations, out of order; exactly
+    16 variable observed cameras."""
+    from bundleadjustment_amd import make_synthetic, pack_window_batch
+    from test_window_pack_cpu import ragged
+    probs = ragged()
+    p = make_synthetic(3, 5, 2, seed=0xBA5E0801)
+    p.obs_cam, p.obs_pt, p.obs_uv = p.obs_cam[:0], p.obs_pt[:0], p.obs_uv[:0]
+    probs.append(p)
+    probs.append(make_synthetic(4, 9, 3, seed=0xBA5E0802))
+    p = make_synthetic(5, 12, 3, seed=0xBA5E0803)
+    d = np.r_[np.arange(10), np.arange(4, 20)[::-1], np.arange(4, 9)]
+    p.obs_cam, p.obs_pt, p.obs_uv = np.r_[p.obs_cam, p.obs_cam[d]], np.r_[p.obs_pt, p.obs_pt[d]], np.r_[p.obs_uv, p.obs_uv[d]]
+    probs.append(p)
+    probs.append(bp.fix_camera(make_synthetic(18, 40, 6, seed=0xBA5E0804), 1))
+    b = pack_window_batch(probs)
+    b.cam_fixed[b.cam_offset[4]:b.cam_offset[5]] = 1
+    return b
+
+
+def write_batch(path, b, with_flags=True):
+    n = len(b.cam_offset) - 1
+    head = np.array([n, len(b.cam_fixed), len(b.pt_fixed), len(b.obs_cam), 3 if with_flags else 0], np.int32)
+    parts = [head, b.cam_offset, b.pt_offset, b.obs_offset]
+    if with_flags:
+        parts += [b.cam_fixed, b.pt_fixed]
+    parts += [b.obs_cam, b.obs_pt, b.obs_uv]
+    path.write_bytes(b"".join(np.ascontiguousarray(a).tobytes() for a in parts))
+
+
+def numpy_structure(b, with_flags=True):
+    """The arrays ba_solve_window_batch uploads, built independently of the
+    C++ loop: lexsort by (point, camera, caller order), bincount + cumsum for
+    both CSRs, the first observation of a (point, camera) group of a variable
+    point carries the camera's compact index."""
+    out = {k: [] for k in ("prob", "cam_vc", "pt_var", "pt_off", "obs_cam", "obs_slot", "uv", "cam_off", "cam_obs")}
+    nv_total = coff = vobs = 0
+    for i in range(len(b.cam_offset) - 1):
+        c0, p0, o0 = int(b.cam_offset[i]), int(b.pt_offset[i]), int(b.obs_offset[i])
+        nc, npt, no = int(b.cam_offset[i + 1]) - c0, int(b.pt_offset[i + 1]) - p0, int(b.obs_offset[i + 1]) - o0
+        oc, op, uv = b.obs_cam[o0:o0 + no], b.obs_pt[o0:o0 + no], b.obs_uv[o0:o0 + no]
+        cfix = b.cam_fixed[c0:c0 + nc] != 0 if with_flags else np.zeros(nc, bool)
+        pfix = b.pt_fixed[p0:p0 + npt] != 0 if with_flags else np.zeros(npt, bool)
+        var_c, var_p = np.zeros(nc, bool), np.zeros(npt, bool)
+        var_c[oc], var_p[op] = True, True
+        var_c &= ~cfix
+        var_p &= ~pfix
+        cam_vc = np.where(var_c, np.cumsum(var_c) - 1, -1).astype(np.int32)
+        nvc = int(var_c.sum())
+        order = np.lexsort((np.arange(no), oc, op))
+        soc, sop = oc[order], op[order]
+        head = np.ones(no, bool)
+        head[1:] = (sop[1:] != sop[:-1]) | (soc[1:] != soc[:-1])
+        v = cam_vc[soc]
+        slot = np.where(head & var_p[sop] & (v >= 0), v, -1)
+        sel = np.flatnonzero(v >= 0)
+        out["prob"].append([c0, p0, o0, nc, npt, no, nvc, nv_total, p0 + i, coff, vobs, 0])
+        out["cam_vc"].append(cam_vc)
+        out["pt_var"].append(var_p.astype(np.uint8))
+        out["pt_off"].append(np.r_[0, np.cumsum(np.bincount(op, minlength=npt))])
+        out["obs_cam"].append(soc)
+        out["obs_slot"].append(slot)
+        out["uv"].append(uv[order].reshape(-1))
+        out["cam_off"].append(np.r_[0, np.cumsum(np.bincount(v[sel], minlength=nvc))])
+        out["cam_obs"].append(sel[np.argsort(v[sel], kind="stable")])
+        nv_total, coff, vobs = nv_total + nvc, coff + nvc + 1, vobs + len(sel)
+    dt = {"pt_var": np.uint8, "uv": np.float32}
+    res = {k: np.concatenate([np.asarray(a).reshape(-1) for a in v]).astype(dt.get(k, np.int32)) for k, v in out.items()}
+    res["NV"] = np.array([nv_total], np.int64)
+    return res
+
+
+def read_structure(path):
+    raw, at, res = path.read_bytes(), 0, {}
+    for k, dt in (("prob", np.int32), ("cam_vc", np.int32), ("pt_var", np.uint8), ("pt_off", np.int32),
+                  ("obs_cam", np.int32), ("obs_slot", np.int32), ("uv", np.float32), ("cam_off", np.int32),
+                  ("cam_obs", np.int32), ("NV", np.int64)):
+        nb = int(np.frombuffer(raw, np.int64, 1, at)[0])
+        res[k] = np.frombuffer(raw, dt, nb // np.dtype(dt).itemsize, at + 8)
+        at += 8 + nb
+    assert at == len(raw)
+    return res
+
+
+def test_batch_packer_under_asan_ubsan(san_build, tmp_path):
+    exe = san_build / "batch_pack_san"
+    b = pack_batch()
+    for with_flags in (True, False):   # (False: cam_fixed / pt_fixed NULL, every observed block variable ...
+        if not with_flags:             #  ... so the 18-camera problem would have 18: leave it out)
+            from bundleadjustment_amd import pack_window_batch
+            from test_window_pack_cpu import ragged
+            b = pack_window_batch(ragged())
+        write_batch(tmp_path / "in.bin", b, with_flags)
+        out = run_clean([exe, tmp_path / "in.bin", tmp_path / "out.bin"]).splitlines()
+        want, got = numpy_structure(b, with_flags), read_structure(tmp_path / "out.bin")
+        for k in want:
+            assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+        assert out[-1] == f"packed {len(b.cam_offset) - 1} problems"
+        if with_flags:   # the batch has the cases it is there for
+            prob = want["prob"].reshape(-1, 12)
+            assert list(prob[3:, 5] == 0) == [True, False, False, False]            # no observation
+            assert prob[4, 6] == 0 and prob[4, 5] > 0                               # every camera constant
+            o0, no = prob[5, 2], prob[5, 5]
+            pairs = np.stack([b.obs_pt[o0:o0 + no], b.obs_cam[o0:o0 + no]], 1)
+            assert len(np.unique(pairs, axis=0)) < no                               # duplicates
+            assert prob[6, 6] == 16 and want["NV"][0] == prob[:, 6].sum()           # the cap
+            assert (want["obs_slot"] >= 0).any() and (want["obs_slot"] < 0).any()
+    # the layout builder, check_offsets and unpack_summary (printed by every run)
+    for A, line in zip((1, 16, 256), out[:3]):
+        al = lambda x: -(-x // A) * A   # noqa: E731
+        c = al(1) + A
+        io = c + al(A + 1)
+        assert line == f"layout {A}: 0 {al(1)} {c} {c} {io} | {c} {io} {io + al(700)}"
+    assert out[3:7] == ["offsets ok", "offsets ok", "offsets 1 fn: off[0] != 0", "offsets 1 fn: off decreases at point 1"]
+    assert out[7] == "summary 4 2 7 5 2 1 | 0.5 0 0 | 0.5 0.5 0.5"
+
+    # malformed batches: refused with the messages the GPU tests match, nothing read out of bounds
+    def refused(mutate, *words):
+        m = pack_batch()
+        mutate(m)
+        write_batch(tmp_path / "bad.bin", m)
+        msg = run_clean([exe, tmp_path / "bad.bin", tmp_path / "bad_out.bin"], rc=3).splitlines()[-1]
+        assert msg.startswith("error 1: ba_solve_window_batch: ") and all(w in msg for w in words), msg
+
+    def local_index(m):
+        m.obs_cam[m.obs_offset[1] + 5] = 7
+
+    def decreasing(m):
+        m.pt_offset = m.pt_offset.copy()
+        m.pt_offset[2] = m.pt_offset[1] - 1
+
+    def seventeen(m):
+        m.cam_fixed[m.cam_offset[6] + 1] = 0
+
+    def first_offset(m):
+        m.obs_offset = m.obs_offset.copy()
+        m.obs_offset[0] = 1
+
+    refused(local_index, "problem 1", "local index out of range")
+    refused(decreasing, "decreases", "problem 1")
+    refused(seventeen, "problem 6", "17")
+    refused(first_offset, "offset[0] != 0")

@@ -2,7 +2,9 @@
 against the oracle on the equivalent one-point problem (test_pose_batch's
 tolerances), the statuses against the float32 restatement evaluated at the
 device's own point, a cross-check against ba_solve_window_batch, bitwise
-reproducibility and the error contract.  Reference: tests/triangulate_ref.py."""
+reproducibility, the error contract, and the staging arenas of the batch entry
+points across growing, shrinking and interleaved calls.  Reference:
+tests/triangulate_ref.py."""
 import ctypes as C
 
 import numpy as np
@@ -340,3 +342,61 @@ def test_errors_name_the_culprit_and_leave_the_context_usable(solver):
     assert lib.ba_triangulate(h, C.byref(tb0), None, None, None, None, None) == 0
     times = solver.triangulate_times()
     assert times.shape == (3,) and np.all(times >= 0) and times[2] >= times[0]
+
+
+# ---------------------------------------------------------------------------
+# 8. the staging arenas of the batch entry points
+# ---------------------------------------------------------------------------
+def test_staging_arenas_grow_shrink_and_interleave_bitwise():
+    """One context through triangulate small -> large -> small, a window
+    batch, pose batches large -> small, a prune and the small triangulate
+    again: each arena grows, is reused for a smaller call, and the features
+    interleave.  Every result equals, bit for bit, the same call on a fresh
+    context."""
+    from bundleadjustment_amd import problem as bp
+    from test_pose_batch import batch_of, f2f_problem
+
+    def tri_scene(nc, npts, k, seed):
+        return R.triangulation_batch(R.all_fixed(make_synthetic(nc, npts, k, seed=seed, perturb=None, anchor=False)))
+
+    small, large = tri_scene(2, 3, 2, 41), tri_scene(8, 300, 4, 42)
+    windows = [bp.fix_camera(make_synthetic(4, 60, 3, seed=43), 1), bp.fix_camera(make_synthetic(3, 40, 3, seed=44), 1)]
+    pose40 = batch_of([f2f_problem(20 + 7 * i, seed=500 + i) for i in range(40)])
+    pose5 = batch_of([f2f_problem(30 + i, seed=600 + i) for i in range(5)])
+    pt_of_obs = np.repeat(np.arange(len(large.pts)), np.diff(large.obs_offset))[:50]
+    uv50 = large.obs_uv[:50].copy()
+    uv50[::7] += 50.0                           # (gross keypoints: both verdicts occur)
+    prune50 = (large.extr, large.cam_center, large.K, large.obs_cam[:50], large.pts[pt_of_obs].astype(np.float32),
+               uv50, np.ones(50, np.float32), np.tile(np.float32([0.0, 100.0]), (50, 1)))
+    opts = Options(max_num_iterations=10)
+
+    def tri(b):
+        def call(s):
+            pts, status, summ = run(s, b, refine=True, options=opts)
+            return [pts.tobytes(), status.tobytes(), summ_array(summ).tobytes()]
+        return call
+
+    def window(s):
+        out, summ = s.solve_window_batch(windows, opts)
+        logs = [[r[f] for r in s.window_iteration_log(i) for f in sorted(r)] for i in range(len(windows))]
+        return [a.tobytes() for cp in out for a in cp] + [summ_array(summ).tobytes(), np.float64(sum(logs, [])).tobytes()]
+
+    def pose(batch):
+        def call(s):
+            out, summ = s.solve_pose_batch(*batch, opts)
+            return [out.tobytes(), summ_array(summ).tobytes()]
+        return call
+
+    def prune(s):
+        return [s.prune(*prune50).tobytes()]
+
+    calls = {"tri3": tri(small), "tri300": tri(large), "window": window, "pose40": pose(pose40), "pose5": pose(pose5),
+             "prune": prune}
+    fresh = {}
+    for name, call in calls.items():
+        with Solver(0) as s:
+            fresh[name] = call(s)
+    assert len(set(fresh["prune"][0])) > 1
+    with Solver(0) as reused:                   # (its arenas start empty: the second call has to grow)
+        for name in ("tri3", "tri300", "tri3", "window", "pose40", "pose5", "prune", "tri3"):
+            assert calls[name](reused) == fresh[name], name
