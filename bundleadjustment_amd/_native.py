@@ -122,6 +122,26 @@ TRI_CHECK_CHEIRALITY, TRI_CHECK_CHI2, TRI_CHECK_SCALE = 1, 2, 4
 TRI_CHECK_ALL = 7
 
 
+class ba_pnp_options(C.Structure):
+    _fields_ = [
+        ("max_hypotheses", C.c_int32), ("min_points", C.c_int32), ("min_inliers", C.c_int32),
+        ("use_prior", C.c_int32), ("refine", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64),
+        ("threshold_px", C.c_double),
+    ]
+
+
+class ba_pnp_result(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("n_inliers", C.c_int32), ("n_inliers_ransac", C.c_int32),
+        ("best_hypothesis", C.c_int32), ("cam_ransac", C.c_double * 6), ("refine", ba_summary),
+    ]
+
+
+# enum ba_pnp_status (include/ba_hip.h)
+PNP_STATUS_NAMES = {0: "OK", 1: "FEW_POINTS", 2: "NO_MODEL", 3: "REFINE_FAILED"}
+PNP_OK, PNP_FEW_POINTS, PNP_NO_MODEL, PNP_REFINE_FAILED = range(4)
+
+
 class ba_covariance_request(C.Structure):
     _fields_ = [
         ("n_cam_pairs", C.c_int32), ("n_points", C.c_int32), ("cam_pairs", C.c_void_p), ("cam_cov", C.c_void_p),
@@ -189,6 +209,12 @@ SIGNATURES = [
     ("ba_triangulate", C.c_int, [C.c_void_p, C.POINTER(ba_tri_batch), C.POINTER(ba_tri_options),
                                  C.POINTER(ba_options), C.c_void_p, C.c_void_p, C.POINTER(ba_summary)]),
     ("ba_triangulate_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ba_pnp_defaults", None, [C.POINTER(ba_pnp_options)]),
+    ("ba_pnp_ransac", C.c_int, [C.c_void_p, C.POINTER(ba_pose_batch), C.POINTER(ba_pnp_options),
+                                C.POINTER(ba_options), C.c_void_p, C.c_void_p, C.POINTER(ba_pnp_result)]),
+    ("ba_pnp_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ba_pnp_hypotheses", C.c_int, [C.c_void_p, C.POINTER(ba_pose_batch), C.POINTER(ba_pnp_options), C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
     ("ba_covariance_ex", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request_ex)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

@@ -357,6 +357,39 @@ struct TriArgs {
 };
 void launch_triangulate(const TriArgs& A, const PoseOpts& o, hipStream_t s);
 
+// batched P3P RANSAC + pose LM on the consensus set (ba_pnp.hip)
+constexpr int kPnpRec = 16;        // doubles per wave record: the packed vote key, R (row-major), t, pad
+struct PnpArgs {
+  int n_prob, H;                   // problems, hypotheses per problem
+  int n_min, inl_min;              // max(4, min_points), max(4, min_inliers)
+  int use_prior, refine;
+  int G;                           // lanes per hypothesis of k_pnp_score: 1 or 8 (pnp_group)
+  unsigned long long seed;
+  double thr2;                     // threshold_px^2
+  double huber_a;
+  // inputs
+  const int* off; const double* prior; const float* K; const double* X; const float2* uv;
+  // scratch
+  double* rec;                     // [n_prob][ceil(H / (64 / G))][kPnpRec]
+  uint8_t* cmask;                  // [n_obs] consensus at cam_ransac
+  int* cnt;                        // [n_prob] its size (0 unless the status is OK)
+  int* coff;                       // [n_prob + 1] dense offsets of the compacted observations
+  double* Xc; float2* uvc;         // the compacted observations, caller order
+  // outputs
+  double* cams_out;                // [n_prob][6]
+  double* cam_ransac;              // [n_prob][6]
+  double* summ;                    // [n_prob][8] (launch_pose_batch's record)
+  int* res;                        // [n_prob][4]: status, n_inliers, n_inliers_ransac, best_hypothesis
+  uint8_t* inlier;                 // [n_obs]
+};
+// ba_pnp_hypotheses: hypotheses [h0, h0 + n) of one problem
+struct PnpDebug {
+  int problem, h0, n;
+  int* sample; int* n_sol; double* Rt; int* count;   // [n][3 | 1 | 48 | 4]
+};
+void launch_pnp(const PnpArgs& A, const PoseOpts& o, hipStream_t s);
+void launch_pnp_hypotheses(const PnpArgs& A, const PnpDebug& D, hipStream_t s);
+
 int grid_for(int n);
 int pt_group_grid(int np);   // grid of the kPtLanes-lanes-per-point kernels
 

@@ -109,15 +109,16 @@ struct ba_ctx {
   unsigned* d_hseq = nullptr;
   unsigned* d_ticket = nullptr;  // k_reduce<true>'s last-workgroup ticket (zero between launches)
   unsigned scal_seq = 0;
-  // staging of ba_solve_pose_batch, ba_solve_window_batch and ba_triangulate
-  // (one each: a call of one never makes another reallocate)
-  StagingArena pose, win, tri;
+  // staging of ba_solve_pose_batch, ba_solve_window_batch, ba_triangulate and
+  // ba_pnp_ransac (one each: a call of one never makes another reallocate)
+  StagingArena pose, win, tri, pnp;
   // ba_solve_window_batch: the last call's logs and times
   std::vector<ba_iteration> win_log;   // [n_problems][win_log_cap]
   std::vector<int> win_log_n;
   int win_log_cap = 0;
   std::vector<double> win_ms;          // ba_window_times of the last call
   std::vector<double> tri_ms;          // ba_triangulate_times of the last call
+  std::vector<double> pnp_ms;          // ba_pnp_times of the last call
 
   // host copies of the sorted structure, kept for the lazily built
   // linear-solver structures (Schur pair lists / PCG duplicate pairs)
@@ -2094,7 +2095,7 @@ int ba_destroy(ba_ctx* ctx) {
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
-  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri}) (void)hipFree(a->dev);
+  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp}) (void)hipFree(a->dev);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -2576,6 +2577,133 @@ int ba_triangulate(ba_ctx* ctx, const ba_tri_batch* b, const ba_tri_options* top
 
 int ba_triangulate_times(ba_ctx* ctx, double* ms, int n) {
   return ctx ? copy_times(ctx->tri_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
+}
+
+// ---------------------------------------------------------------------------
+// ba_pnp_ransac: host side.  Validation and section layout are plain C++
+// (check_pnp, pnp_layout: host/ba_batch_pack.hpp); one staging upload, the
+// launches of ba_pnp.hip, one download.  The context's current problem is not
+// touched.
+// ---------------------------------------------------------------------------
+void ba_pnp_defaults(ba_pnp_options* opt) {
+  if (opt) pnp_defaults(*opt);
+}
+
+namespace {
+
+// the batch into the arena's host copy and onto the device; the kernel
+// arguments that name the inputs
+PnpArgs pnp_stage(ba_ctx* ctx, const ba_pose_batch* b, const ba_pnp_options& p, const PnpLayout& P, const std::string& fn) {
+  const size_t N = b->n_problems, NO = b->obs_offset[N];
+  HIP_OK(hipSetDevice(ctx->device));
+  ctx->pnp.reserve(ctx, P.L.total, fn);
+  std::vector<char>& h = ctx->pnp.host;
+  h.assign(P.L.io_b, 0);
+  stage(h, P.off, b->obs_offset, sizeof(int) * (N + 1));
+  if (b->cams) stage(h, P.prior, b->cams, sizeof(double) * 6 * N);
+  stage(h, P.K, b->K, sizeof(float) * 9 * N);
+  stage(h, P.X, b->pts, sizeof(double) * 3 * NO);
+  stage(h, P.uv, b->obs_uv, sizeof(float) * 2 * NO);
+  char* d = ctx->pnp.dev;
+  HIP_OK(hipMemcpyAsync(d, h.data(), P.L.in_b, hipMemcpyHostToDevice, ctx->stream));
+  PnpArgs A{};
+  A.n_prob = (int)N; A.H = p.max_hypotheses;
+  A.n_min = std::max(4, p.min_points); A.inl_min = std::max(4, p.min_inliers);
+  A.use_prior = p.use_prior; A.refine = p.refine;
+  A.seed = p.seed; A.thr2 = p.threshold_px * p.threshold_px; A.huber_a = b->huber_a;
+  A.off = at<const int>(d, P.off); A.prior = at<const double>(d, P.prior); A.K = at<const float>(d, P.K);
+  A.X = at<const double>(d, P.X); A.uv = at<const float2>(d, P.uv);
+  return A;
+}
+
+}  // namespace
+
+int ba_pnp_ransac(ba_ctx* ctx, const ba_pose_batch* b, const ba_pnp_options* popt, const ba_options* lm,
+                  double* cams_out, uint8_t* inlier, ba_pnp_result* results) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_pnp_ransac: ";
+    const ba_options o = options_or_default(lm);
+    const ba_pnp_options p = check_pnp(fn.c_str(), b, popt, &o);
+    const size_t N = b->n_problems;
+    if (N == 0) return;
+    const size_t NO = b->obs_offset[N];
+    if (!cams_out || (NO > 0 && !inlier)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const double t0 = now_s();
+    const int G = pnp_group(N, p.max_hypotheses);
+    const PnpLayout P = pnp_layout(N, NO, p.max_hypotheses, G, 0);
+    PnpArgs A = pnp_stage(ctx, b, p, P, fn);
+    A.G = G;
+    char* d = ctx->pnp.dev;
+    A.rec = at<double>(d, P.rec); A.cmask = at<uint8_t>(d, P.cmask); A.cnt = at<int>(d, P.cnt); A.coff = at<int>(d, P.coff);
+    A.Xc = at<double>(d, P.Xc); A.uvc = at<float2>(d, P.uvc);
+    A.cams_out = at<double>(d, P.cams_out); A.cam_ransac = at<double>(d, P.cam_ransac); A.summ = at<double>(d, P.summ);
+    A.res = at<int>(d, P.res); A.inlier = at<uint8_t>(d, P.inlier);
+    const double t_prep = now_s() - t0;
+    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
+    launch_pnp(A, pose_opts(o), ctx->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
+    std::vector<char>& h = ctx->pnp.host;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    float kernel_ms = 0.0f;
+    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
+    std::memcpy(cams_out, h.data() + P.cams_out, sizeof(double) * 6 * N);
+    if (NO) std::memcpy(inlier, h.data() + P.inlier, NO);
+    const double wall = now_s() - t0;
+    ctx->pnp_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * wall};
+    if (results)
+      for (size_t i = 0; i < N; ++i) {
+        ba_pnp_result& r = results[i];
+        const int* ri = at<const int>(h.data(), P.res) + 4 * i;
+        r = ba_pnp_result{};
+        r.status = ri[0]; r.n_inliers = ri[1]; r.n_inliers_ransac = ri[2]; r.best_hypothesis = ri[3];
+        std::memcpy(r.cam_ransac, h.data() + P.cam_ransac + sizeof(double) * 6 * i, sizeof(double) * 6);
+        if (p.refine && (ri[0] == BA_PNP_OK || ri[0] == BA_PNP_REFINE_FAILED))
+          r.refine = unpack_summary(at<const double>(h.data(), P.summ) + 8 * i, wall, true);
+      }
+  });
+}
+
+int ba_pnp_times(ba_ctx* ctx, double* ms, int n) {
+  return ctx ? copy_times(ctx->pnp_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
+}
+
+int ba_pnp_hypotheses(ba_ctx* ctx, const ba_pose_batch* b, const ba_pnp_options* popt, int problem, int h0, int n,
+                      int32_t* sample, int32_t* n_sol, double* Rt, int32_t* count) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_pnp_hypotheses: ";
+    const ba_pnp_options p = check_pnp(fn.c_str(), b, popt, nullptr);
+    if (problem < 0 || problem >= b->n_problems)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "problem " + std::to_string(problem) + " out of range"};
+    if (h0 < 0 || n < 0 || (long long)h0 + n > p.max_hypotheses)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "hypotheses [" + std::to_string(h0) + ", " + std::to_string((long long)h0 + n) +
+                                                 ") outside max_hypotheses " + std::to_string(p.max_hypotheses)};
+    if (n == 0) return;
+    if (!sample || !n_sol || !Rt || !count) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const int nobs = b->obs_offset[problem + 1] - b->obs_offset[problem];
+    const bool prior_only = p.use_prior && h0 == 0 && n == 1;
+    if (nobs < 3 && !prior_only)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "problem " + std::to_string(problem) + " has fewer than 3 observations"};
+    const size_t N = b->n_problems, NO = b->obs_offset[N];
+    const PnpLayout P = pnp_layout(N, NO, p.max_hypotheses, 1, (size_t)n);
+    PnpArgs A = pnp_stage(ctx, b, p, P, fn);
+    A.G = 1;
+    char* d = ctx->pnp.dev;
+    const PnpDebug D{problem, h0, n, at<int>(d, P.dbg_sample), at<int>(d, P.dbg_nsol), at<double>(d, P.dbg_Rt),
+                     at<int>(d, P.dbg_count)};
+    launch_pnp_hypotheses(A, D, ctx->stream);
+    HIP_OK(hipGetLastError());
+    std::vector<char>& h = ctx->pnp.host;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(sample, h.data() + P.dbg_sample, sizeof(int32_t) * 3 * n);
+    std::memcpy(n_sol, h.data() + P.dbg_nsol, sizeof(int32_t) * n);
+    std::memcpy(Rt, h.data() + P.dbg_Rt, sizeof(double) * 48 * n);
+    std::memcpy(count, h.data() + P.dbg_count, sizeof(int32_t) * 4 * n);
+  });
 }
 
 int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double* Hcc, double* gc, double* S,

@@ -1,7 +1,7 @@
 // ba_batch_pack.hpp — host-only packing shared by the batch entry points of
 // ba_solver.hip: the error type, the section layout of a staging buffer, the
-// CSR-offset validation, the summary record, and the structure build of
-// ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
+// CSR-offset validation, the summary record, the validation and layout of
+// ba_pnp_ransac, and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
 // plain C++17 without a HIP header and runs under ASan + UBSan
 // (tests/cpp/batch_pack.cpp, `make -C tests/cpp sanitize`).
 #pragma once
@@ -48,6 +48,81 @@ inline ba_summary unpack_summary(const double* rec, double wall, bool split_time
   S.total_time_s = wall;
   if (split_times) S.linearize_time_s = S.solve_time_s = wall;
   return S;
+}
+
+// ---------------------------------------------------------------------------
+// ba_pnp_ransac / ba_pnp_hypotheses
+// ---------------------------------------------------------------------------
+inline void pnp_defaults(ba_pnp_options& o) {
+  o.max_hypotheses = 1000; o.min_points = 7; o.min_inliers = 6; o.use_prior = 1; o.refine = 1; o.reserved = 0;
+  o.seed = 0; o.threshold_px = 8.0;
+}
+
+// Everything the kernels index with or branch on, checked on the host: the
+// batch, the options (returned with the defaults applied) and, with refine,
+// the LM options.  lm: the resolved LM options, or null when they are not read.
+inline ba_pnp_options check_pnp(const char* fn, const ba_pose_batch* b, const ba_pnp_options* popt, const ba_options* lm) {
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what}; };
+  if (!b || b->n_problems < 0) throw invalid("bad batch");
+  ba_pnp_options p;
+  if (popt) p = *popt; else pnp_defaults(p);
+  if (p.max_hypotheses < 1 || p.max_hypotheses > 65536)
+    throw invalid("max_hypotheses " + std::to_string(p.max_hypotheses) + " outside 1 .. 65536");
+  if (p.min_points < 0) throw invalid("min_points " + std::to_string(p.min_points) + " is negative");
+  if (p.min_inliers < 0) throw invalid("min_inliers " + std::to_string(p.min_inliers) + " is negative");
+  if (p.use_prior != 0 && p.use_prior != 1) throw invalid("unknown use_prior " + std::to_string(p.use_prior));
+  if (p.refine != 0 && p.refine != 1) throw invalid("unknown refine " + std::to_string(p.refine));
+  if (!(p.threshold_px > 0.0 && p.threshold_px <= 1.7976931348623157e308))
+    throw invalid("threshold_px must be positive and finite");
+  if (p.refine && lm) {
+    if (lm->linear_solver != BA_DENSE_SCHUR) throw invalid("linear_solver must be BA_DENSE_SCHUR");
+    if (lm->precision != BA_FP64) throw invalid("precision must be BA_FP64");
+  }
+  const int n = b->n_problems;
+  if (n == 0) return p;
+  if (!b->obs_offset || !b->K) throw invalid("null array");
+  if (p.use_prior && !b->cams) throw invalid("use_prior is set but cams is null");
+  check_offsets(fn, "obs_offset", b->obs_offset, n);
+  if (b->obs_offset[n] > 0 && (!b->pts || !b->obs_uv)) throw invalid("null array");
+  return p;
+}
+
+// Lanes per hypothesis of the scoring kernel: 8 while the batch, at one wave
+// per 64 hypotheses, would occupy at most 64 waves (a single frame leaves the
+// chip idle and is bound by the serial walk over its points), else 1.  The
+// votes are integers, so the results do not depend on the choice.
+inline int pnp_group(size_t N, int H) { return N * (((size_t)H + 63) / 64) <= 64 ? 8 : 1; }
+
+// The staging buffer of the two entries.  ba_pnp_ransac (dbg_n == 0): the
+// batch | cams_out, cam_ransac, LM summaries, result records, inlier mask |
+// wave records, consensus mask, counts, dense offsets, compacted observations.
+// ba_pnp_hypotheses (dbg_n > 0): the batch | the four inspection arrays.
+struct PnpLayout {
+  SectionLayout L{256};
+  size_t off = 0, prior = 0, K = 0, X = 0, uv = 0;
+  size_t cams_out = 0, cam_ransac = 0, summ = 0, res = 0, inlier = 0;
+  size_t rec = 0, cmask = 0, cnt = 0, coff = 0, Xc = 0, uvc = 0;
+  size_t dbg_sample = 0, dbg_nsol = 0, dbg_Rt = 0, dbg_count = 0;
+};
+inline PnpLayout pnp_layout(size_t N, size_t NO, int H, int G, size_t dbg_n) {
+  PnpLayout P;
+  SectionLayout& L = P.L;
+  P.off = L.add(sizeof(int32_t) * (N + 1)); P.prior = L.add(sizeof(double) * 6 * N); P.K = L.add(sizeof(float) * 9 * N);
+  P.X = L.add(sizeof(double) * 3 * NO); P.uv = L.add(sizeof(float) * 2 * NO);
+  L.end_inputs();
+  if (dbg_n > 0) {
+    P.dbg_sample = L.add(sizeof(int32_t) * 3 * dbg_n); P.dbg_nsol = L.add(sizeof(int32_t) * dbg_n);
+    P.dbg_Rt = L.add(sizeof(double) * 48 * dbg_n); P.dbg_count = L.add(sizeof(int32_t) * 4 * dbg_n);
+    L.end_outputs();
+    return P;
+  }
+  P.cams_out = L.add(sizeof(double) * 6 * N); P.cam_ransac = L.add(sizeof(double) * 6 * N);
+  P.summ = L.add(sizeof(double) * 8 * N); P.res = L.add(sizeof(int32_t) * 4 * N); P.inlier = L.add(NO);
+  L.end_outputs();
+  const size_t hpw = 64 / (size_t)G, nw = ((size_t)H + hpw - 1) / hpw;
+  P.rec = L.add(sizeof(double) * 16 * nw * N); P.cmask = L.add(NO); P.cnt = L.add(sizeof(int32_t) * N);
+  P.coff = L.add(sizeof(int32_t) * (N + 1)); P.Xc = L.add(sizeof(double) * 3 * NO); P.uvc = L.add(sizeof(float) * 2 * NO);
+  return P;
 }
 
 // One problem of ba_solve_window_batch as the kernel (ba_window.hip) reads it

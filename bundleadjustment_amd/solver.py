@@ -75,7 +75,19 @@ class Summary:
     solve_time_s: float
 
 
+@dataclass
+class PnpResult:
+    """ba_pnp_result: status is an N.PNP_* code."""
+    status: int
+    n_inliers: int
+    n_inliers_ransac: int
+    best_hypothesis: int
+    cam_ransac: np.ndarray
+    refine: Summary
+
+
 ITER_FIELDS = [f for f, _ in N.ba_iteration._fields_]
+PNP_OPTION_FIELDS = [f for f, _ in N.ba_pnp_options._fields_ if f != "reserved"]
 
 
 class Solver:
@@ -505,6 +517,79 @@ class Solver:
         out = np.empty(max(n, 0))
         if n > 0:
             self.lib.ba_triangulate_times(self.h, _ptr(out), n)
+        return out
+
+    # -- robust absolute pose ---------------------------------------------
+    def _pnp_batch(self, obs_offset, cams, K, pts, obs_uv, huber_a, pnp_options):
+        off = np.ascontiguousarray(obs_offset, dtype=np.int32).reshape(-1)
+        n = max(off.size - 1, 0)
+        c = None if cams is None else np.ascontiguousarray(cams, dtype=np.float64).reshape(n, 6)
+        k = np.ascontiguousarray(K, dtype=np.float32).reshape(n, 9)
+        x = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        uv = np.ascontiguousarray(obs_uv, dtype=np.float32).reshape(-1, 2)
+        if x.shape[0] != uv.shape[0] or (n and off[-1] > uv.shape[0]):
+            raise ValueError("pnp: pts, obs_uv and obs_offset disagree on the number of observations")
+        b = N.ba_pose_batch(n_problems=n, reserved=0, obs_offset=_ptr(off), cams=_ptr(c), K=_ptr(k), pts=_ptr(x),
+                            obs_uv=_ptr(uv), huber_a=float(huber_a))
+        p = N.ba_pnp_options()
+        self.lib.ba_pnp_defaults(C.byref(p))
+        for key, val in pnp_options.items():
+            if key not in PNP_OPTION_FIELDS:
+                raise TypeError(f"pnp: unknown option {key!r}")
+            setattr(p, key, float(val) if key == "threshold_px" else int(val))
+        return b, p, n, uv.shape[0], (off, c, k, x, uv)
+
+    def pnp_ransac(self, obs_offset, cams, K, pts, obs_uv, *, options: Options | None = None,
+                   huber_a: float = HUBER_A, **pnp_options
+                   ) -> tuple[np.ndarray, np.ndarray, list[PnpResult]]:
+        """Batched robust absolute pose (ba_pnp_ransac): P3P RANSAC on the
+        device, the whole hypothesis budget scored in parallel, then the pose
+        LM of solve_pose_batch on the consensus set.  The arguments are
+        solve_pose_batch's; cams is the prior (None with use_prior=0).
+        pnp_options: max_hypotheses, min_points, min_inliers, use_prior,
+        refine, seed, threshold_px (defaults: ba_pnp_defaults); options: the
+        LM's.  Returns (cams (n, 6), inlier mask (n_obs,) bool in caller
+        order, results)."""
+        b, p, n, n_obs, _keep = self._pnp_batch(obs_offset, cams, K, pts, obs_uv, huber_a, pnp_options)
+        o = (options or Options()).to_c()
+        out = np.zeros((n, 6))
+        inl = np.zeros(n_obs, np.uint8)
+        res = (N.ba_pnp_result * max(n, 1))()
+        self._check(self.lib.ba_pnp_ransac(self.h, C.byref(b), C.byref(p), C.byref(o), _ptr(out), _ptr(inl), res),
+                    "ba_pnp_ransac")
+        results = []
+        for r in list(res)[:n]:
+            s = r.refine
+            results.append(PnpResult(
+                r.status, r.n_inliers, r.n_inliers_ransac, r.best_hypothesis, np.array(r.cam_ransac[:]),
+                Summary(s.initial_cost, s.final_cost, s.num_iterations, s.num_successful_steps,
+                        s.num_unsuccessful_steps, N.TERMINATION_NAMES.get(s.termination_type, str(s.termination_type)),
+                        s.total_time_s, s.linearize_time_s, s.solve_time_s)))
+        return out, inl.astype(bool), results
+
+    def pnp_hypotheses(self, obs_offset, cams, K, pts, obs_uv, problem: int, h0: int, n: int, **pnp_options) -> dict:
+        """Hypotheses h0 .. h0+n-1 of one problem exactly as pnp_ransac forms
+        and scores them (ba_pnp_hypotheses): sample (n, 3) local observation
+        indices (-1: the prior), n_sol (n,), R (n, 4, 3, 3), t (n, 4, 3) and
+        count (n, 4), solutions in their fixed order."""
+        b, p, _n, _no, _keep = self._pnp_batch(obs_offset, cams, K, pts, obs_uv, 0.0, pnp_options)
+        m = max(int(n), 0)
+        sample = np.zeros((m, 3), np.int32)
+        n_sol = np.zeros(m, np.int32)
+        Rt = np.zeros((m, 4, 12))
+        count = np.zeros((m, 4), np.int32)
+        self._check(self.lib.ba_pnp_hypotheses(self.h, C.byref(b), C.byref(p), int(problem), int(h0), int(n),
+                                               _ptr(sample), _ptr(n_sol), _ptr(Rt), _ptr(count)), "ba_pnp_hypotheses")
+        return {"sample": sample, "n_sol": n_sol, "R": Rt[:, :, :9].reshape(m, 4, 3, 3).copy(),
+                "t": Rt[:, :, 9:].copy(), "count": count}
+
+    def pnp_times(self) -> np.ndarray:
+        """Times (ms) of the last pnp_ransac: host preparation (wall), the
+        kernels (device), the whole call (wall)."""
+        n = self.lib.ba_pnp_times(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            self.lib.ba_pnp_times(self.h, _ptr(out), n)
         return out
 
     def synchronize(self):

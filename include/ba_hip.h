@@ -445,6 +445,127 @@ int ba_triangulate(ba_ctx* ctx, const ba_tri_batch* batch, const ba_tri_options*
  * before the first call).  Diagnostic. */
 int ba_triangulate_times(ba_ctx* ctx, double* ms, int n);
 
+/* Batched robust absolute pose: P3P RANSAC on the device, refined by the pose
+ * LM of ba_solve_pose_batch.  This is the reference's EstimationType::PNP row
+ * (SfMHelper::estimatePoseUsingPnP, SfMHelper.cpp:16-104), which wanted
+ * cv::solvePnPRansac(..., true, 1000, 8.0, 0.99, inliers) (line 72), fell back
+ * to plain solvePnP and never fills its inlier vector.  The input is a
+ * ba_pose_batch: problem i owns observations [obs_offset[i], obs_offset[i+1])
+ * of constant points; cams is the prior (useExtrinsicGuess) and may be NULL
+ * only when use_prior == 0.
+ *
+ * Sampling, pinned so that any implementation draws the same triples and
+ * independent of the problem's place in the batch.  With n the problem's
+ * observation count and mix() the splitmix64 finaliser
+ *   mix(z): z ^= z>>30; z *= 0xBF58476D1CE4E5B9; z ^= z>>27; z *= 0x94D049BB133111EB; z ^= z>>31
+ *   draw(h, j, m) = ((mix(seed + (4h + j + 1) * 0x9E3779B97F4A7C15) >> 32) * m) >> 32   (uint64, wrapping)
+ *   a = draw(h, 0, n)
+ *   b = draw(h, 1, n-1);  if b >= a: ++b
+ *   c = draw(h, 2, n-2);  if c >= min(a, b): ++c;  then if c >= max(a, b): ++c
+ * hypothesis h samples the local observations (a, b, c), always distinct.
+ * With use_prior, hypothesis 0 is the prior itself and hypotheses 1 ..
+ * max_hypotheses-1 sample with their own h.
+ *
+ * Minimal solver (csrc/ba_p3p.h, the same text on the device and in host
+ * programs): P3P in fp64 on the unit bearings K^-1 [u, v, 1] of the float
+ * pixels promoted to double.  With the distances s_i to the three points it
+ * eliminates u = s2/s1 from the two conics the law of cosines gives in (u, v =
+ * s3/s1), solves the resultant quartic in v in closed form (resolvent cubic,
+ * two real quadratics, two Newton steps per root), recovers u linearly,
+ * polishes (s1, s2, s3) by five Newton steps on the three distance equations
+ * and takes the rigid motion between the triads of the two triangles.  It
+ * returns 0-4 world->camera poses (R, t) with all three sample points at
+ * positive depth.  The order of a hypothesis's solutions is fixed: increasing
+ * quartic root v = s3/s1.  A double root may be returned twice.
+ *
+ * Scoring: an observation is an inlier of a pose iff, with p = R X + t and
+ * q = K p accumulated as the pose LM accumulates its candidate residual,
+ * q2 > 0 and (q0/q2 - u)^2 + (q1/q2 - v)^2 <= threshold_px^2.  A solution's
+ * score is its inlier count, a hypothesis's score its best solution (ties: the
+ * lower solution index), the winner the best hypothesis (ties: the lower h).
+ * Counts are integers, so the result does not depend on a reduction order.
+ * There is no confidence parameter: the whole budget is evaluated in parallel,
+ * so an early exit would save nothing.
+ *
+ * After the vote the winner is converted to angle-axis
+ * (ceres::RotationMatrixToAngleAxis): cam_ransac = [w, t]; when the prior wins
+ * it is returned with its own bits.  The consensus set
+ * is the predicate at cam_ransac through ceres::AngleAxisToRotationMatrix, as
+ * every residual of the library; n_inliers_ransac is its size.  With refine,
+ * cams_out is bit for bit what ba_solve_pose_batch returns for the consensus
+ * observations in caller order, started at cam_ransac, with lm and huber_a;
+ * without, cams_out = cam_ransac.  inlier[o] (caller order) is the predicate
+ * at cams_out, n_inliers its sum per problem.
+ *
+ * Statuses: a problem with fewer than max(4, min_points) observations is
+ * BA_PNP_FEW_POINTS (SfMHelper.cpp:46 keeps the prior for size() <= 6); a best
+ * consensus (the winner's vote) below max(4, min_inliers) is BA_PNP_NO_MODEL.
+ * Both return the prior in cams_out (zeros without a prior) and in cam_ransac,
+ * inlier all 0, best_hypothesis -1 and a zero summary.  If the LM ends
+ * BA_FAILURE the status is BA_PNP_REFINE_FAILED and cams_out = cam_ransac.  A
+ * problem's status never affects its neighbours.
+ *
+ * Contract, as ba_triangulate: a problem's output bits depend only on its own
+ * data and the options, not on its place in the batch or on the other
+ * problems; two calls give bitwise equal output; the context's current problem
+ * is untouched (a ba_solve before and after is bit for bit what it would have
+ * been); no collective; the call blocks until the results are on the host.
+ *
+ * Errors (the context stays usable; nothing is launched; all validation is on
+ * the host):
+ *   BA_ERR_INVALID_ARGUMENT  a NULL required array, obs_offset[0] != 0 or a
+ *                            decreasing obs_offset (the message names the
+ *                            problem), max_hypotheses outside 1 .. 65536,
+ *                            negative min_points / min_inliers, use_prior or
+ *                            refine not 0 / 1, a threshold_px that is not
+ *                            positive and finite, cams == NULL with
+ *                            use_prior; with refine: linear_solver !=
+ *                            BA_DENSE_SCHUR or precision != BA_FP64,
+ *   BA_ERR_OUT_OF_MEMORY     the scratch cannot be allocated. */
+enum ba_pnp_status { BA_PNP_OK = 0, BA_PNP_FEW_POINTS = 1, BA_PNP_NO_MODEL = 2, BA_PNP_REFINE_FAILED = 3 };
+
+typedef struct {
+  int32_t max_hypotheses;  /* default 1000 (the reference's commented call); 1 .. 65536 */
+  int32_t min_points;      /* default 7: fewer than max(4, min_points) observations is FEW_POINTS */
+  int32_t min_inliers;     /* default 6: best consensus below max(4, min_inliers) is NO_MODEL */
+  int32_t use_prior;       /* default 1: hypothesis 0 is batch->cams[problem] (useExtrinsicGuess), not a sample */
+  int32_t refine;          /* default 1: LM on the consensus set */
+  int32_t reserved;
+  uint64_t seed;           /* default 0 */
+  double  threshold_px;    /* default 8.0; inlier iff r0^2 + r1^2 <= threshold_px^2 */
+} ba_pnp_options;
+
+typedef struct {
+  int32_t status;             /* ba_pnp_status */
+  int32_t n_inliers;          /* of `inlier`, at cams_out */
+  int32_t n_inliers_ransac;   /* consensus set at cam_ransac */
+  int32_t best_hypothesis;    /* index h of the winner; -1 without a model */
+  double  cam_ransac[6];      /* the winner as [w, t], before refinement */
+  ba_summary refine;          /* the LM's summary (zeros when refine == 0 or no model; time fields: the call's wall time) */
+} ba_pnp_result;
+
+void ba_pnp_defaults(ba_pnp_options* opt);
+int ba_pnp_ransac(ba_ctx* ctx, const ba_pose_batch* batch, const ba_pnp_options* popt /* NULL = defaults */,
+                  const ba_options* lm /* NULL = defaults; read when refine */,
+                  double* cams_out /* [6*n_problems] */, uint8_t* inlier /* [n_obs], caller order */,
+                  ba_pnp_result* results /* [n_problems], may be NULL */);
+/* Times (ms) of the last successful ba_pnp_ransac: [0] host preparation
+ * (validation, staging, upload enqueue; wall), [1] the kernels (device, HIP
+ * events), [2] the whole call (wall).  Copies min(n, 3) values, returns 3 (0
+ * before the first call).  Diagnostic. */
+int ba_pnp_times(ba_ctx* ctx, double* ms, int n);
+/* Test / inspection entry point: hypotheses h0 .. h0+n-1 (within
+ * max_hypotheses) of problem `problem` exactly as ba_pnp_ransac forms and
+ * scores them (min_points is not applied; the problem needs 3 observations
+ * unless only the prior is asked for).  sample: the local observation indices
+ * (-1 x3 for the prior); n_sol: 0 .. 4; Rt: the solutions in their fixed
+ * order, R row-major, then t (unused entries zero); count: their consensus
+ * counts at threshold_px.  Same errors as ba_pnp_ransac, plus a problem or
+ * hypothesis range out of bounds. */
+int ba_pnp_hypotheses(ba_ctx* ctx, const ba_pose_batch* batch, const ba_pnp_options* popt, int problem, int h0, int n,
+                      int32_t* sample /* [3*n] */, int32_t* n_sol /* [n] */, double* Rt /* [n][4][12] */,
+                      int32_t* count /* [n][4] */);
+
 /* Test / inspection entry point: the state inside ceres::Solve's
  * SchurComplementSolver (Optimizer.cpp:242, DENSE_SCHUR) for one step.
  * Linearises at the current parameters with iteration-0 Jacobi scaling, then
