@@ -142,6 +142,37 @@ PNP_STATUS_NAMES = {0: "OK", 1: "FEW_POINTS", 2: "NO_MODEL", 3: "REFINE_FAILED"}
 PNP_OK, PNP_FEW_POINTS, PNP_NO_MODEL, PNP_REFINE_FAILED = range(4)
 
 
+class ba_two_view_batch(C.Structure):
+    _fields_ = [
+        ("n_pairs", C.c_int32), ("reserved", C.c_int32), ("match_offset", C.c_void_p), ("K1", C.c_void_p),
+        ("K2", C.c_void_p), ("uv1", C.c_void_p), ("uv2", C.c_void_p),
+    ]
+
+
+class ba_two_view_options(C.Structure):
+    _fields_ = [
+        ("max_hypotheses", C.c_int32), ("min_points", C.c_int32), ("min_inliers", C.c_int32), ("min_good", C.c_int32),
+        ("model", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("threshold_px", C.c_double),
+        ("h_ratio", C.c_double),
+    ]
+
+
+class ba_two_view_result(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("model", C.c_int32), ("n_inliers", C.c_int32), ("n_good", C.c_int32),
+        ("n_good_second", C.c_int32), ("best_hypothesis_e", C.c_int32), ("best_hypothesis_h", C.c_int32),
+        ("votes_e", C.c_int32), ("votes_h", C.c_int32), ("reserved", C.c_int32), ("score_e", C.c_double),
+        ("score_h", C.c_double), ("E", C.c_double * 9), ("H", C.c_double * 9), ("cam", C.c_double * 6),
+        ("normal", C.c_double * 3),
+    ]
+
+
+# enum ba_tv_status, ba_tv_model (include/ba_hip.h)
+TV_STATUS_NAMES = {0: "OK", 1: "FEW_POINTS", 2: "NO_MODEL", 3: "NO_POSE"}
+TV_OK, TV_FEW_POINTS, TV_NO_MODEL, TV_NO_POSE = range(4)
+TV_AUTO, TV_ESSENTIAL, TV_HOMOGRAPHY = range(3)
+
+
 class ba_covariance_request(C.Structure):
     _fields_ = [
         ("n_cam_pairs", C.c_int32), ("n_points", C.c_int32), ("cam_pairs", C.c_void_p), ("cam_cov", C.c_void_p),
@@ -215,6 +246,13 @@ SIGNATURES = [
     ("ba_pnp_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("ba_pnp_hypotheses", C.c_int, [C.c_void_p, C.POINTER(ba_pose_batch), C.POINTER(ba_pnp_options), C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ba_two_view_defaults", None, [C.POINTER(ba_two_view_options)]),
+    ("ba_two_view_ransac", C.c_int, [C.c_void_p, C.POINTER(ba_two_view_batch), C.POINTER(ba_two_view_options),
+                                     C.c_void_p, C.POINTER(ba_two_view_result)]),
+    ("ba_two_view_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ba_two_view_hypotheses", C.c_int, [C.c_void_p, C.POINTER(ba_two_view_batch), C.POINTER(ba_two_view_options),
+                                         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
     ("ba_covariance_ex", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request_ex)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

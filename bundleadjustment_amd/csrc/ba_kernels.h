@@ -390,6 +390,36 @@ struct PnpDebug {
 void launch_pnp(const PnpArgs& A, const PoseOpts& o, hipStream_t s);
 void launch_pnp_hypotheses(const PnpArgs& A, const PnpDebug& D, hipStream_t s);
 
+// batched two-view relative pose: E / H RANSAC, model choice, pose recovery (ba_two_view.hip)
+constexpr int kTvRes = 40;         // doubles per result record: status, model, n_inliers, n_good, n_good_second,
+                                   // best_e, best_h, votes_e, votes_h, S_E, S_H, E[9], H[9], cam[6], normal[3], pad
+struct TvArgs {
+  int n_pair, H;                   // pairs, hypotheses per pair
+  int n_min, inl_min, good_min;    // max(8, min_points), max(8, min_inliers), max(1, min_good)
+  int model;                       // ba_tv_model
+  int G;                           // lanes per hypothesis of k_tv_score: 1 or 8 (pnp_group)
+  unsigned long long seed;
+  double thr2;                     // threshold_px^2
+  double h_ratio;
+  // inputs
+  const int* off; const float* K1; const float* K2;
+  const float4* m;                 // [n_matches] (u1, v1, u2, v2)
+  // scratch
+  double* models;                  // [n_pair][H][18]: E, H row-major
+  int* valid;                      // [n_pair][H][2]
+  unsigned long long* rec;         // [n_pair][ceil(H / (64 / G))][2]: the packed vote keys of E and H
+  // outputs
+  double* res;                     // [n_pair][kTvRes]
+  uint8_t* inlier;                 // [n_matches]
+};
+// ba_two_view_hypotheses: hypotheses [h0, h0 + n) of one pair (models / valid hold n slots)
+struct TvDebug {
+  int pair, h0, n;
+  int* sample; int* count;         // [n][8 | 2]
+};
+void launch_two_view(const TvArgs& A, hipStream_t s);
+void launch_two_view_hypotheses(const TvArgs& A, const TvDebug& D, hipStream_t s);
+
 int grid_for(int n);
 int pt_group_grid(int np);   // grid of the kPtLanes-lanes-per-point kernels
 

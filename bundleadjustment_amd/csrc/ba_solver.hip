@@ -109,9 +109,10 @@ struct ba_ctx {
   unsigned* d_hseq = nullptr;
   unsigned* d_ticket = nullptr;  // k_reduce<true>'s last-workgroup ticket (zero between launches)
   unsigned scal_seq = 0;
-  // staging of ba_solve_pose_batch, ba_solve_window_batch, ba_triangulate and
-  // ba_pnp_ransac (one each: a call of one never makes another reallocate)
-  StagingArena pose, win, tri, pnp;
+  // staging of ba_solve_pose_batch, ba_solve_window_batch, ba_triangulate,
+  // ba_pnp_ransac and ba_two_view_ransac (one each: a call of one never makes
+  // another reallocate)
+  StagingArena pose, win, tri, pnp, tv;
   // ba_solve_window_batch: the last call's logs and times
   std::vector<ba_iteration> win_log;   // [n_problems][win_log_cap]
   std::vector<int> win_log_n;
@@ -119,6 +120,7 @@ struct ba_ctx {
   std::vector<double> win_ms;          // ba_window_times of the last call
   std::vector<double> tri_ms;          // ba_triangulate_times of the last call
   std::vector<double> pnp_ms;          // ba_pnp_times of the last call
+  std::vector<double> tv_ms;           // ba_two_view_times of the last call
 
   // host copies of the sorted structure, kept for the lazily built
   // linear-solver structures (Schur pair lists / PCG duplicate pairs)
@@ -2095,7 +2097,7 @@ int ba_destroy(ba_ctx* ctx) {
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
-  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp}) (void)hipFree(a->dev);
+  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv}) (void)hipFree(a->dev);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -2703,6 +2705,131 @@ int ba_pnp_hypotheses(ba_ctx* ctx, const ba_pose_batch* b, const ba_pnp_options*
     std::memcpy(n_sol, h.data() + P.dbg_nsol, sizeof(int32_t) * n);
     std::memcpy(Rt, h.data() + P.dbg_Rt, sizeof(double) * 48 * n);
     std::memcpy(count, h.data() + P.dbg_count, sizeof(int32_t) * 4 * n);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// ba_two_view_ransac: host side.  Validation and section layout are plain C++
+// (check_two_view, two_view_layout: host/ba_batch_pack.hpp); one staging
+// upload, the launches of ba_two_view.hip, one download.  The context's
+// current problem is not touched.
+// ---------------------------------------------------------------------------
+void ba_two_view_defaults(ba_two_view_options* opt) {
+  if (opt) two_view_defaults(*opt);
+}
+
+namespace {
+
+// the batch into the arena's host copy and onto the device; the kernel
+// arguments that name the inputs
+TvArgs two_view_stage(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_view_options& p, const TwoViewLayout& P,
+                      const std::string& fn) {
+  const size_t N = b->n_pairs, NM = b->match_offset[N];
+  HIP_OK(hipSetDevice(ctx->device));
+  ctx->tv.reserve(ctx, P.L.total, fn);
+  std::vector<char>& h = ctx->tv.host;
+  h.assign(P.L.io_b, 0);
+  stage(h, P.off, b->match_offset, sizeof(int) * (N + 1));
+  stage(h, P.K1, b->K1, sizeof(float) * 9 * N);
+  stage(h, P.K2, b->K2 ? b->K2 : b->K1, sizeof(float) * 9 * N);
+  two_view_pack_matches(b, NM, at<float>(h.data(), P.m));
+  char* d = ctx->tv.dev;
+  HIP_OK(hipMemcpyAsync(d, h.data(), P.L.in_b, hipMemcpyHostToDevice, ctx->stream));
+  TvArgs A{};
+  A.n_pair = (int)N; A.H = p.max_hypotheses;
+  A.n_min = std::max(8, p.min_points); A.inl_min = std::max(8, p.min_inliers); A.good_min = std::max(1, p.min_good);
+  A.model = p.model; A.G = 1;
+  A.seed = p.seed; A.thr2 = p.threshold_px * p.threshold_px; A.h_ratio = p.h_ratio;
+  A.off = at<const int>(d, P.off); A.K1 = at<const float>(d, P.K1); A.K2 = at<const float>(d, P.K2);
+  A.m = at<const float4>(d, P.m);
+  A.models = at<double>(d, P.models); A.valid = at<int>(d, P.valid);
+  return A;
+}
+
+}  // namespace
+
+int ba_two_view_ransac(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_view_options* opt, uint8_t* inlier,
+                       ba_two_view_result* results) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_two_view_ransac: ";
+    const ba_two_view_options p = check_two_view(fn.c_str(), b, opt);
+    const size_t N = b->n_pairs;
+    if (N == 0) return;
+    const size_t NM = b->match_offset[N];
+    if (!results || (NM > 0 && !inlier)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const double t0 = now_s();
+    const int G = pnp_group(N, p.max_hypotheses);
+    const TwoViewLayout P = two_view_layout(N, NM, p.max_hypotheses, G, 0);
+    TvArgs A = two_view_stage(ctx, b, p, P, fn);
+    A.G = G;
+    char* d = ctx->tv.dev;
+    A.rec = at<unsigned long long>(d, P.rec); A.res = at<double>(d, P.res); A.inlier = at<uint8_t>(d, P.inlier);
+    const double t_prep = now_s() - t0;
+    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
+    launch_two_view(A, ctx->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
+    std::vector<char>& h = ctx->tv.host;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    float kernel_ms = 0.0f;
+    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
+    if (NM) std::memcpy(inlier, h.data() + P.inlier, NM);
+    for (size_t i = 0; i < N; ++i) {
+      const double* r = at<const double>(h.data(), P.res) + (size_t)kTvRes * i;
+      ba_two_view_result& o = results[i];
+      o = ba_two_view_result{};
+      o.status = (int)r[0]; o.model = (int)r[1]; o.n_inliers = (int)r[2]; o.n_good = (int)r[3]; o.n_good_second = (int)r[4];
+      o.best_hypothesis_e = (int)r[5]; o.best_hypothesis_h = (int)r[6]; o.votes_e = (int)r[7]; o.votes_h = (int)r[8];
+      o.score_e = r[9]; o.score_h = r[10];
+      std::memcpy(o.E, r + 11, sizeof(double) * 9);
+      std::memcpy(o.H, r + 20, sizeof(double) * 9);
+      std::memcpy(o.cam, r + 29, sizeof(double) * 6);
+      std::memcpy(o.normal, r + 35, sizeof(double) * 3);
+    }
+    ctx->tv_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * (now_s() - t0)};
+  });
+}
+
+int ba_two_view_times(ba_ctx* ctx, double* ms, int n) {
+  return ctx ? copy_times(ctx->tv_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
+}
+
+int ba_two_view_hypotheses(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_view_options* opt, int pair, int h0, int n,
+                           int32_t* sample, double* E, double* H, int32_t* valid, int32_t* count) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_two_view_hypotheses: ";
+    const ba_two_view_options p = check_two_view(fn.c_str(), b, opt);
+    if (pair < 0 || pair >= b->n_pairs)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " out of range"};
+    if (h0 < 0 || n < 0 || (long long)h0 + n > p.max_hypotheses)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "hypotheses [" + std::to_string(h0) + ", " + std::to_string((long long)h0 + n) +
+                                                 ") outside max_hypotheses " + std::to_string(p.max_hypotheses)};
+    if (n == 0) return;
+    if (!sample || !E || !H || !valid || !count) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    if (b->match_offset[pair + 1] - b->match_offset[pair] < 8)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " has fewer than 8 matches"};
+    const size_t N = b->n_pairs, NM = b->match_offset[N];
+    const TwoViewLayout P = two_view_layout(N, NM, p.max_hypotheses, 1, (size_t)n);
+    TvArgs A = two_view_stage(ctx, b, p, P, fn);
+    A.n_min = 8;
+    char* d = ctx->tv.dev;
+    const TvDebug D{pair, h0, n, at<int>(d, P.dbg_sample), at<int>(d, P.dbg_count)};
+    launch_two_view_hypotheses(A, D, ctx->stream);
+    HIP_OK(hipGetLastError());
+    std::vector<char>& h = ctx->tv.host;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(sample, h.data() + P.dbg_sample, sizeof(int32_t) * 8 * n);
+    std::memcpy(valid, h.data() + P.valid, sizeof(int32_t) * 2 * n);
+    std::memcpy(count, h.data() + P.dbg_count, sizeof(int32_t) * 2 * n);
+    const double* m = at<const double>(h.data(), P.models);
+    for (int i = 0; i < n; ++i) {
+      std::memcpy(E + 9 * (size_t)i, m + 18 * (size_t)i, sizeof(double) * 9);
+      std::memcpy(H + 9 * (size_t)i, m + 18 * (size_t)i + 9, sizeof(double) * 9);
+    }
   });
 }
 

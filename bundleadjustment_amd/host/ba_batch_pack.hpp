@@ -1,7 +1,7 @@
 // ba_batch_pack.hpp — host-only packing shared by the batch entry points of
 // ba_solver.hip: the error type, the section layout of a staging buffer, the
 // CSR-offset validation, the summary record, the validation and layout of
-// ba_pnp_ransac, and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
+// ba_pnp_ransac and ba_two_view_ransac, and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
 // plain C++17 without a HIP header and runs under ASan + UBSan
 // (tests/cpp/batch_pack.cpp, `make -C tests/cpp sanitize`).
 #pragma once
@@ -123,6 +123,77 @@ inline PnpLayout pnp_layout(size_t N, size_t NO, int H, int G, size_t dbg_n) {
   P.rec = L.add(sizeof(double) * 16 * nw * N); P.cmask = L.add(NO); P.cnt = L.add(sizeof(int32_t) * N);
   P.coff = L.add(sizeof(int32_t) * (N + 1)); P.Xc = L.add(sizeof(double) * 3 * NO); P.uvc = L.add(sizeof(float) * 2 * NO);
   return P;
+}
+
+// ---------------------------------------------------------------------------
+// ba_two_view_ransac / ba_two_view_hypotheses
+// ---------------------------------------------------------------------------
+inline void two_view_defaults(ba_two_view_options& o) {
+  o.max_hypotheses = 1000; o.min_points = 8; o.min_inliers = 8; o.min_good = 101; o.model = BA_TV_AUTO; o.reserved = 0;
+  o.seed = 0; o.threshold_px = 1.0; o.h_ratio = 0.4;
+}
+
+// Everything the kernels index with or branch on, checked on the host; the
+// options are returned with the defaults applied.
+inline ba_two_view_options check_two_view(const char* fn, const ba_two_view_batch* b, const ba_two_view_options* opt) {
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what}; };
+  if (!b || b->n_pairs < 0) throw invalid("bad batch");
+  ba_two_view_options p;
+  if (opt) p = *opt; else two_view_defaults(p);
+  if (p.max_hypotheses < 1 || p.max_hypotheses > 65536)
+    throw invalid("max_hypotheses " + std::to_string(p.max_hypotheses) + " outside 1 .. 65536");
+  if (p.min_points < 0) throw invalid("min_points " + std::to_string(p.min_points) + " is negative");
+  if (p.min_inliers < 0) throw invalid("min_inliers " + std::to_string(p.min_inliers) + " is negative");
+  if (p.min_good < 0) throw invalid("min_good " + std::to_string(p.min_good) + " is negative");
+  if (p.model != BA_TV_AUTO && p.model != BA_TV_ESSENTIAL && p.model != BA_TV_HOMOGRAPHY)
+    throw invalid("unknown model " + std::to_string(p.model));
+  if (!(p.threshold_px > 0.0 && p.threshold_px <= 1.7976931348623157e308))
+    throw invalid("threshold_px must be positive and finite");
+  if (!(p.h_ratio >= 0.0 && p.h_ratio <= 1.0)) throw invalid("h_ratio must lie in [0, 1]");
+  const int n = b->n_pairs;
+  if (n == 0) return p;
+  if (!b->match_offset || !b->K1) throw invalid("null array");
+  check_offsets(fn, "match_offset", b->match_offset, n, "pair");
+  if (b->match_offset[n] > 0 && (!b->uv1 || !b->uv2)) throw invalid("null array");
+  return p;
+}
+
+// The staging buffer of the two entries.  ba_two_view_ransac (dbg_n == 0):
+// offsets, K1, K2, matches as (u1, v1, u2, v2) | result records, inlier mask |
+// models, validity, wave records.  ba_two_view_hypotheses (dbg_n > 0): the
+// batch | samples, models, validity, counts of the dbg_n hypotheses.
+struct TwoViewLayout {
+  SectionLayout L{256};
+  size_t off = 0, K1 = 0, K2 = 0, m = 0;
+  size_t res = 0, inlier = 0;
+  size_t models = 0, valid = 0, rec = 0;
+  size_t dbg_sample = 0, dbg_count = 0;
+};
+inline TwoViewLayout two_view_layout(size_t N, size_t NM, int H, int G, size_t dbg_n) {
+  TwoViewLayout P;
+  SectionLayout& L = P.L;
+  P.off = L.add(sizeof(int32_t) * (N + 1)); P.K1 = L.add(sizeof(float) * 9 * N); P.K2 = L.add(sizeof(float) * 9 * N);
+  P.m = L.add(sizeof(float) * 4 * NM);
+  L.end_inputs();
+  if (dbg_n > 0) {
+    P.dbg_sample = L.add(sizeof(int32_t) * 8 * dbg_n); P.models = L.add(sizeof(double) * 18 * dbg_n);
+    P.valid = L.add(sizeof(int32_t) * 2 * dbg_n); P.dbg_count = L.add(sizeof(int32_t) * 2 * dbg_n);
+    L.end_outputs();
+    return P;
+  }
+  P.res = L.add(sizeof(double) * 40 * N); P.inlier = L.add(NM);
+  L.end_outputs();
+  const size_t hpw = 64 / (size_t)G, nw = ((size_t)H + hpw - 1) / hpw;
+  P.models = L.add(sizeof(double) * 18 * (size_t)H * N); P.valid = L.add(sizeof(int32_t) * 2 * (size_t)H * N);
+  P.rec = L.add(sizeof(uint64_t) * 2 * nw * N);
+  return P;
+}
+// The matches of a batch as the kernels read them: (u1, v1, u2, v2) per match
+inline void two_view_pack_matches(const ba_two_view_batch* b, size_t NM, float* dst) {
+  for (size_t k = 0; k < NM; ++k) {
+    dst[4 * k] = b->uv1[2 * k]; dst[4 * k + 1] = b->uv1[2 * k + 1];
+    dst[4 * k + 2] = b->uv2[2 * k]; dst[4 * k + 3] = b->uv2[2 * k + 1];
+  }
 }
 
 // One problem of ba_solve_window_batch as the kernel (ba_window.hip) reads it

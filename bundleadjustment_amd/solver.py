@@ -86,8 +86,30 @@ class PnpResult:
     refine: Summary
 
 
+@dataclass
+class TwoViewResult:
+    """ba_two_view_result: status is an N.TV_* code, model N.TV_ESSENTIAL or
+    N.TV_HOMOGRAPHY; cam = [w, t] maps frame 1 to frame 2."""
+    status: int
+    model: int
+    n_inliers: int
+    n_good: int
+    n_good_second: int
+    best_hypothesis_e: int
+    best_hypothesis_h: int
+    votes_e: int
+    votes_h: int
+    score_e: float
+    score_h: float
+    E: np.ndarray
+    H: np.ndarray
+    cam: np.ndarray
+    normal: np.ndarray
+
+
 ITER_FIELDS = [f for f, _ in N.ba_iteration._fields_]
 PNP_OPTION_FIELDS = [f for f, _ in N.ba_pnp_options._fields_ if f != "reserved"]
+TV_OPTION_FIELDS = [f for f, _ in N.ba_two_view_options._fields_ if f != "reserved"]
 
 
 class Solver:
@@ -590,6 +612,71 @@ class Solver:
         out = np.empty(max(n, 0))
         if n > 0:
             self.lib.ba_pnp_times(self.h, _ptr(out), n)
+        return out
+
+    # -- two-view relative pose -------------------------------------------
+    def _two_view_batch(self, match_offset, K1, K2, uv1, uv2, tv_options):
+        off = np.ascontiguousarray(match_offset, dtype=np.int32).reshape(-1)
+        n = max(off.size - 1, 0)
+        k1 = np.ascontiguousarray(K1, dtype=np.float32).reshape(n, 9)
+        k2 = None if K2 is None else np.ascontiguousarray(K2, dtype=np.float32).reshape(n, 9)
+        a = np.ascontiguousarray(uv1, dtype=np.float32).reshape(-1, 2)
+        b2 = np.ascontiguousarray(uv2, dtype=np.float32).reshape(-1, 2)
+        if a.shape[0] != b2.shape[0] or (n and off[-1] > a.shape[0]):
+            raise ValueError("two_view: uv1, uv2 and match_offset disagree on the number of matches")
+        b = N.ba_two_view_batch(n_pairs=n, reserved=0, match_offset=_ptr(off), K1=_ptr(k1), K2=_ptr(k2), uv1=_ptr(a),
+                                uv2=_ptr(b2))
+        p = N.ba_two_view_options()
+        self.lib.ba_two_view_defaults(C.byref(p))
+        for key, val in tv_options.items():
+            if key not in TV_OPTION_FIELDS:
+                raise TypeError(f"two_view: unknown option {key!r}")
+            setattr(p, key, float(val) if key in ("threshold_px", "h_ratio") else int(val))
+        return b, p, n, a.shape[0], (off, k1, k2, a, b2)
+
+    def two_view_ransac(self, match_offset, K1, K2, uv1, uv2, **tv_options
+                        ) -> tuple[np.ndarray, list[TwoViewResult]]:
+        """Batched two-view relative pose (ba_two_view_ransac): E and H RANSAC
+        on the device, the reference's model choice, decomposition and the
+        positive-depth vote.  Pair i owns matches match_offset[i] ..
+        match_offset[i+1]; K1 / K2 (n, 9) col-major (K2 None: K1); uv1 / uv2
+        (n_matches, 2) float32 pixels.  tv_options: max_hypotheses,
+        min_points, min_inliers, min_good, model, seed, threshold_px, h_ratio
+        (defaults: ba_two_view_defaults).  Returns (inlier mask (n_matches,)
+        bool, results)."""
+        b, p, n, nm, _keep = self._two_view_batch(match_offset, K1, K2, uv1, uv2, tv_options)
+        inl = np.zeros(nm, np.uint8)
+        res = (N.ba_two_view_result * max(n, 1))()
+        self._check(self.lib.ba_two_view_ransac(self.h, C.byref(b), C.byref(p), _ptr(inl), res), "ba_two_view_ransac")
+        results = [TwoViewResult(r.status, r.model, r.n_inliers, r.n_good, r.n_good_second, r.best_hypothesis_e,
+                                 r.best_hypothesis_h, r.votes_e, r.votes_h, r.score_e, r.score_h,
+                                 np.array(r.E[:]).reshape(3, 3), np.array(r.H[:]).reshape(3, 3), np.array(r.cam[:]),
+                                 np.array(r.normal[:])) for r in list(res)[:n]]
+        return inl.astype(bool), results
+
+    def two_view_hypotheses(self, match_offset, K1, K2, uv1, uv2, pair: int, h0: int, n: int, **tv_options) -> dict:
+        """Hypotheses h0 .. h0+n-1 of one pair exactly as two_view_ransac forms
+        and scores them (ba_two_view_hypotheses): sample (n, 8) local match
+        indices, E and H (n, 3, 3), valid and count (n, 2) as (E, H)."""
+        b, p, _n, _nm, _keep = self._two_view_batch(match_offset, K1, K2, uv1, uv2, tv_options)
+        m = max(int(n), 0)
+        sample = np.zeros((m, 8), np.int32)
+        E = np.zeros((m, 3, 3))
+        H = np.zeros((m, 3, 3))
+        valid = np.zeros((m, 2), np.int32)
+        count = np.zeros((m, 2), np.int32)
+        self._check(self.lib.ba_two_view_hypotheses(self.h, C.byref(b), C.byref(p), int(pair), int(h0), int(n),
+                                                    _ptr(sample), _ptr(E), _ptr(H), _ptr(valid), _ptr(count)),
+                    "ba_two_view_hypotheses")
+        return {"sample": sample, "E": E, "H": H, "valid": valid, "count": count}
+
+    def two_view_times(self) -> np.ndarray:
+        """Times (ms) of the last two_view_ransac: host preparation (wall), the
+        kernels (device), the whole call (wall)."""
+        n = self.lib.ba_two_view_times(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            self.lib.ba_two_view_times(self.h, _ptr(out), n)
         return out
 
     def synchronize(self):

@@ -566,6 +566,156 @@ int ba_pnp_hypotheses(ba_ctx* ctx, const ba_pose_batch* batch, const ba_pnp_opti
                       int32_t* sample /* [3*n] */, int32_t* n_sol /* [n] */, double* Rt /* [n][4][12] */,
                       int32_t* count /* [n][4] */);
 
+/* Batched two-view relative pose: essential-matrix and homography RANSAC on
+ * the device, the model choice, the decomposition and the positive-depth vote.
+ * This is the reference's EstimationType "2d2d" row (SfMHelper::recoverPose,
+ * SfMHelper.cpp:498-742: cv::findEssentialMat, cv::findHomography, the
+ * ORB-SLAM-style scores, cv::recoverPose / cv::decomposeHomographyMat).  Pair
+ * i owns matches [match_offset[i], match_offset[i+1]); uv1 / uv2 are the
+ * matched pixels of frame 1 / frame 2.  The semantics are pinned here, not
+ * taken from a third-party library.
+ *
+ * Sampling.  With n the pair's match count and mix() the splitmix64 finaliser
+ * of ba_pnp_ransac
+ *   draw(h, j, m) = ((mix(seed + (16h + j + 1) * 0x9E3779B97F4A7C15) >> 32) * m) >> 32   (uint64, wrapping)
+ * hypothesis h takes eight distinct local indices: for j = 0 .. 7,
+ * c = draw(h, j, n - j); for each earlier pick p in increasing order,
+ * if c >= p: ++c.  The essential hypothesis uses all eight, the homography
+ * hypothesis the first four.  There is no prior hypothesis.
+ *
+ * Minimal solvers (csrc/ba_two_view.h, the same text on the device and in
+ * host programs), fp64 on the float pixels promoted to double.
+ *   E: the normalised eight-point on the bearings K^-1 [u, v, 1] dehomogenised
+ *      to (x, y, 1): each side Hartley-normalised over the eight samples, the
+ *      null vector of the 8x9 system, E = T2^T E^ T1 scaled to Frobenius norm
+ *      1 (either sign).
+ *   H: the four-point DLT on Hartley-normalised pixels: the null vector of
+ *      the 8x9 system, H = T2^-1 H^ T1 scaled to norm 1 with the sign that
+ *      transfers the first sample with w > 0 (x2 ~ H x1).
+ * The null vector is x = H_0 .. H_7 e_8 of the Householder QR of the
+ * transposed system (reflector k from the remainder of row k): it works on
+ * the matrix itself and is backward stable.  A model with a non-finite entry
+ * is invalid; H is also invalid if |det H| <= 1e-10 r0 r1 r2 (r_i the norms
+ * of its rows).  An invalid model scores 0 and cannot win.
+ *
+ * Vote.  With K^-1 by cofactors, F = K2^-T (E K1^-1) (row-major products, the
+ * inner index increasing) and x = [u, v, 1]:
+ *   a = F x1 (a_i = F_i0 u1 + F_i1 v1 + F_i2), d2^2 = (u2 a0 + v2 a1 + a2)^2 / (a0^2 + a1^2)
+ *   b = F^T x2 likewise,                       d1^2 = (u1 b0 + v1 b1 + b2)^2 / (b0^2 + b1^2)
+ *   E-inlier iff d1^2 <= threshold_px^2 and d2^2 <= threshold_px^2.
+ *   p = H x1 (p_i = H_i0 u1 + H_i1 v1 + H_i2), e2^2 = (u2 - p0/p2)^2 + (v2 - p1/p2)^2,
+ *   e1^2 the same with H^-1 (cofactors / determinant) on x2 against x1; a
+ *   transfer with w = p2 <= 0 is an outlier;
+ *   H-inlier iff e1^2 <= threshold_px^2 and e2^2 <= threshold_px^2.
+ * Votes are integer counts over all matches of the pair; the winner per model
+ * is the largest count, ties to the lower h.
+ *
+ * After the vote, per pair.  A model is available if its winner's vote is at
+ * least max(8, min_inliers); a model that is not reports its vote, hypothesis
+ * -1 and a zero matrix.  The E winner is projected to the essential
+ * manifold (3x3 SVD by one-sided Jacobi, singular values (1, 1, 0) / sqrt 2,
+ * U and V made rotations by u3 = u1 x u2, v3 = v1 x v2).  The final masks are
+ * the predicates at the projected E and at H, tightened as the reference's
+ * post-marking: an E-inlier also needs d1^2, d2^2 <= 3.841 (lines 611-629), an
+ * H-inlier both transfer errors <= 5.991 (lines 559-577).  S_E = sum over the
+ * E-mask of (5.991 - d1^2) + (5.991 - d2^2), S_H the same over the H-mask with
+ * (e1^2, e2^2); both are summed in a fixed order (lane l takes matches l,
+ * l + 64, ..; then an xor butterfly 32, 16, .., 1).  BA_TV_AUTO picks the
+ * homography iff (float)(S_H / (S_H + S_E)) > h_ratio (line 642), else E; a
+ * chosen (or forced) model that is not available is BA_TV_NO_MODEL.
+ * Candidates, in this order:
+ *   E (4): (U W V^T, +u3), (U W V^T, -u3), (U W^T V^T, +u3), (U W^T V^T, -u3),
+ *          W = [0 -1 0; 1 0 0; 0 0 1];
+ *   H (8): the SVD decomposition of K2^-1 H K1 = U diag(d1, d2, d3) V^T
+ *          (Faugeras, in the form of ORB-SLAM's ReconstructH): candidates
+ *          0 .. 3 the case d' = +d2, 4 .. 7 the case d' = -d2, within each the
+ *          signs (e1, e3) = (+,+) (+,-) (-,+) (-,-) of the normal's first and
+ *          third SVD coordinate; n is returned with n_z >= 0, |t| = 1.  There
+ *          are none when d1 / d2 < 1.00001 or d2 / d3 < 1.00001.
+ * A candidate's vote is the number of mask inliers with positive depth in
+ * both views: (l1, l2) from the 2x2 least-squares solve of l2 b2 = l1 R b1 + t
+ * on the dehomogenised bearings; a determinant <= 1e-12 |R b1|^2 |b2|^2 is not
+ * good.  The best vote wins; ties go to the larger |n_z| for H (the
+ * reference's heuristic, lines 697-711), then to the lower candidate index.
+ * n_good < max(1, min_good) is BA_TV_NO_POSE.  cam = [w, t] maps frame 1 to
+ * frame 2 (x2 ~ R x1 + t, |t| = 1, w = ceres::RotationMatrixToAngleAxis(R));
+ * the reference's pose is its inverse.  No refit follows: callers refine with
+ * ba_triangulate and the window BA.
+ *
+ * Statuses: fewer than max(8, min_points) matches is BA_TV_FEW_POINTS.  Every
+ * failure returns cam = 0, normal = 0, n_inliers = 0, inlier all 0 and both
+ * best_hypothesis fields -1; FEW_POINTS and NO_MODEL zero the rest of the
+ * record, NO_POSE keeps model, votes, scores, E, H, n_good and n_good_second.
+ * A pair's status never affects its neighbours.
+ *
+ * Contract, as ba_pnp_ransac: a pair's output bits depend only on its own
+ * data and the options, not on its place in the batch or on the other pairs;
+ * two calls give bitwise equal output; the context's current problem is
+ * untouched; no collective; the call blocks until the results are on the host.
+ *
+ * Errors (the context stays usable; nothing is launched; all validation is on
+ * the host):
+ *   BA_ERR_INVALID_ARGUMENT  a NULL required array (K2 may be NULL),
+ *                            match_offset[0] != 0 or a decreasing match_offset
+ *                            (the message names the pair), max_hypotheses
+ *                            outside 1 .. 65536, negative min_points /
+ *                            min_inliers / min_good, an unknown model, a
+ *                            threshold_px that is not positive and finite, an
+ *                            h_ratio outside [0, 1],
+ *   BA_ERR_OUT_OF_MEMORY     the scratch cannot be allocated. */
+enum ba_tv_status { BA_TV_OK = 0, BA_TV_FEW_POINTS = 1, BA_TV_NO_MODEL = 2, BA_TV_NO_POSE = 3 };
+enum ba_tv_model  { BA_TV_AUTO = 0, BA_TV_ESSENTIAL = 1, BA_TV_HOMOGRAPHY = 2 };
+
+typedef struct {            /* pair i owns matches [match_offset[i], match_offset[i+1]) */
+  int32_t n_pairs, reserved;
+  const int32_t* match_offset;   /* [n_pairs+1], [0] = 0, non-decreasing */
+  const float*   K1;             /* [9*n_pairs] col-major, frame 1 */
+  const float*   K2;             /* [9*n_pairs]; NULL = K1 (the reference uses frame1's for both) */
+  const float*   uv1;            /* [2*n_matches] keypoints1[queryIdx].pt */
+  const float*   uv2;            /* [2*n_matches] keypoints2[trainIdx].pt */
+} ba_two_view_batch;
+
+typedef struct {
+  int32_t max_hypotheses;  /* default 1000; 1 .. 65536 */
+  int32_t min_points;      /* default 8: fewer than max(8, min_points) matches is FEW_POINTS */
+  int32_t min_inliers;     /* default 8: a winner's vote below max(8, min_inliers) is NO_MODEL */
+  int32_t min_good;        /* default 101: the reference's `inliers <= 100 -> false` (SfMHelper.cpp:656) */
+  int32_t model;           /* default BA_TV_AUTO */
+  int32_t reserved;
+  uint64_t seed;           /* default 0 */
+  double  threshold_px;    /* default 1.0: the reference's RANSAC thresholds (lines 532, 536) */
+  double  h_ratio;         /* default 0.4 (line 643) */
+} ba_two_view_options;
+
+typedef struct {
+  int32_t status, model;               /* model: the one the pose came from (ESSENTIAL / HOMOGRAPHY) */
+  int32_t n_inliers;                   /* of `inlier`, final mask of the chosen model */
+  int32_t n_good, n_good_second;       /* positive-depth votes: best and runner-up candidate */
+  int32_t best_hypothesis_e, best_hypothesis_h;   /* -1 without a model */
+  int32_t votes_e, votes_h;            /* the winners' RANSAC votes */
+  int32_t reserved;
+  double  score_e, score_h;            /* S_E, S_H */
+  double  E[9], H[9];                  /* row-major, Frobenius norm 1; E after the essential projection */
+  double  cam[6];                      /* [w, t]: frame 1 -> frame 2 (x2 ~ R x1 + t), |t| = 1, ceres angle-axis */
+  double  normal[3];                   /* plane normal in frame 1 (HOMOGRAPHY), else 0 */
+} ba_two_view_result;
+
+void ba_two_view_defaults(ba_two_view_options* opt);
+int ba_two_view_ransac(ba_ctx* ctx, const ba_two_view_batch* batch, const ba_two_view_options* opt /* NULL = defaults */,
+                       uint8_t* inlier /* [n_matches] */, ba_two_view_result* results /* [n_pairs] */);
+/* Times (ms) of the last successful ba_two_view_ransac, as ba_pnp_times:
+ * [0] host preparation, [1] the kernels (device), [2] the whole call. */
+int ba_two_view_times(ba_ctx* ctx, double* ms, int n);
+/* Test / inspection entry point: hypotheses h0 .. h0+n-1 (within
+ * max_hypotheses) of pair `pair` exactly as ba_two_view_ransac forms and
+ * scores them (min_points is not applied; the pair needs 8 matches).  sample:
+ * the eight local match indices; E, H: the models, row-major (zeros when
+ * invalid); valid and count: (E, H) per hypothesis.  Same errors as
+ * ba_two_view_ransac, plus a pair or hypothesis range out of bounds. */
+int ba_two_view_hypotheses(ba_ctx* ctx, const ba_two_view_batch* batch, const ba_two_view_options* opt, int pair, int h0,
+                           int n, int32_t* sample /* [8*n] */, double* E /* [9*n] */, double* H /* [9*n] */,
+                           int32_t* valid /* [2*n]: E, H */, int32_t* count /* [2*n] */);
+
 /* Test / inspection entry point: the state inside ceres::Solve's
  * SchurComplementSolver (Optimizer.cpp:242, DENSE_SCHUR) for one step.
  * Linearises at the current parameters with iteration-0 Jacobi scaling, then
