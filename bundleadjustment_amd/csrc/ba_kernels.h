@@ -392,7 +392,8 @@ void launch_pnp_hypotheses(const PnpArgs& A, const PnpDebug& D, hipStream_t s);
 
 // batched two-view relative pose: E / H RANSAC, model choice, pose recovery (ba_two_view.hip)
 constexpr int kTvRes = 40;         // doubles per result record: status, model, n_inliers, n_good, n_good_second,
-                                   // best_e, best_h, votes_e, votes_h, S_E, S_H, E[9], H[9], cam[6], normal[3], pad
+                                   // best_e, best_h, votes_e, votes_h, S_E, S_H, E[9], H[9], cam[6], normal[3],
+                                   // best_solution_e (five-point), pad
 struct TvArgs {
   int n_pair, H;                   // pairs, hypotheses per pair
   int n_min, inl_min, good_min;    // max(8, min_points), max(8, min_inliers), max(1, min_good)
@@ -408,6 +409,12 @@ struct TvArgs {
   double* models;                  // [n_pair][H][18]: E, H row-major
   int* valid;                      // [n_pair][H][2]
   unsigned long long* rec;         // [n_pair][ceil(H / (64 / G))][2]: the packed vote keys of E and H
+  // the five-point E solver (e5 != 0; the arrays exist only then): slot s * H + h holds solution s of hypothesis h
+  int e5;
+  int G5;                          // lanes per slot of k_tv_score5: 1 or 8 (pnp_group over the 10 H slots)
+  double* models5;                 // [n_pair][10][H][9], zeros past n_sol
+  int* nsol5;                      // [n_pair][H]
+  unsigned long long* rec5;        // [n_pair][ceil(10 H / (64 / G5))]: the packed vote key of E
   // outputs
   double* res;                     // [n_pair][kTvRes]
   uint8_t* inlier;                 // [n_matches]
@@ -416,9 +423,11 @@ struct TvArgs {
 struct TvDebug {
   int pair, h0, n;
   int* sample; int* count;         // [n][8 | 2]
+  int* count5;                     // ba_two_view_hypotheses_e5: [n][10] (models5 / nsol5 hold n hypotheses)
 };
 void launch_two_view(const TvArgs& A, hipStream_t s);
 void launch_two_view_hypotheses(const TvArgs& A, const TvDebug& D, hipStream_t s);
+void launch_two_view_hypotheses_e5(const TvArgs& A, const TvDebug& D, hipStream_t s);
 
 int grid_for(int n);
 int pt_group_grid(int np);   // grid of the kPtLanes-lanes-per-point kernels

@@ -2760,11 +2760,17 @@ int ba_two_view_ransac(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_vie
     if (!results || (NM > 0 && !inlier)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
     const double t0 = now_s();
     const int G = pnp_group(N, p.max_hypotheses);
-    const TwoViewLayout P = two_view_layout(N, NM, p.max_hypotheses, G, 0);
+    const bool e5 = p.reserved == BA_TV_E_FIVE_POINT;
+    const int G5 = pnp_group(N, 10 * p.max_hypotheses);   // the vote of the five-point solutions runs over 10 H slots
+    const TwoViewLayout P = two_view_layout(N, NM, p.max_hypotheses, G, 0, e5, G5);
     TvArgs A = two_view_stage(ctx, b, p, P, fn);
     A.G = G;
     char* d = ctx->tv.dev;
     A.rec = at<unsigned long long>(d, P.rec); A.res = at<double>(d, P.res); A.inlier = at<uint8_t>(d, P.inlier);
+    if (e5) {
+      A.e5 = 1; A.G5 = G5;
+      A.models5 = at<double>(d, P.models5); A.nsol5 = at<int>(d, P.nsol5); A.rec5 = at<unsigned long long>(d, P.rec5);
+    }
     const double t_prep = now_s() - t0;
     HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
     launch_two_view(A, ctx->stream);
@@ -2782,6 +2788,7 @@ int ba_two_view_ransac(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_vie
       o = ba_two_view_result{};
       o.status = (int)r[0]; o.model = (int)r[1]; o.n_inliers = (int)r[2]; o.n_good = (int)r[3]; o.n_good_second = (int)r[4];
       o.best_hypothesis_e = (int)r[5]; o.best_hypothesis_h = (int)r[6]; o.votes_e = (int)r[7]; o.votes_h = (int)r[8];
+      o.reserved = (int)r[38];
       o.score_e = r[9]; o.score_h = r[10];
       std::memcpy(o.E, r + 11, sizeof(double) * 9);
       std::memcpy(o.H, r + 20, sizeof(double) * 9);
@@ -2830,6 +2837,45 @@ int ba_two_view_hypotheses(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two
       std::memcpy(E + 9 * (size_t)i, m + 18 * (size_t)i, sizeof(double) * 9);
       std::memcpy(H + 9 * (size_t)i, m + 18 * (size_t)i + 9, sizeof(double) * 9);
     }
+  });
+}
+
+int ba_two_view_hypotheses_e5(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_view_options* opt, int pair, int h0, int n,
+                              int32_t* sample, int32_t* n_sol, double* E, int32_t* count) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_two_view_hypotheses_e5: ";
+    const ba_two_view_options p = check_two_view(fn.c_str(), b, opt);
+    if (pair < 0 || pair >= b->n_pairs)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " out of range"};
+    if (h0 < 0 || n < 0 || (long long)h0 + n > p.max_hypotheses)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "hypotheses [" + std::to_string(h0) + ", " + std::to_string((long long)h0 + n) +
+                                                 ") outside max_hypotheses " + std::to_string(p.max_hypotheses)};
+    if (n == 0) return;
+    if (!sample || !n_sol || !E || !count) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    if (b->match_offset[pair + 1] - b->match_offset[pair] < 8)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " has fewer than 8 matches"};
+    const size_t N = b->n_pairs, NM = b->match_offset[N];
+    const TwoViewLayout P = two_view_layout(N, NM, p.max_hypotheses, 1, (size_t)n, true);
+    TvArgs A = two_view_stage(ctx, b, p, P, fn);
+    A.n_min = 8;
+    char* d = ctx->tv.dev;
+    A.e5 = 1; A.G5 = 1;
+    A.models = nullptr; A.valid = nullptr;   // (the layout has no eight-point sections)
+    A.models5 = at<double>(d, P.models5); A.nsol5 = at<int>(d, P.nsol5);
+    TvDebug D{pair, h0, n, at<int>(d, P.dbg_sample), nullptr, at<int>(d, P.dbg_count5)};
+    launch_two_view_hypotheses_e5(A, D, ctx->stream);
+    HIP_OK(hipGetLastError());
+    std::vector<char>& h = ctx->tv.host;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(sample, h.data() + P.dbg_sample, sizeof(int32_t) * 8 * n);
+    std::memcpy(n_sol, h.data() + P.nsol5, sizeof(int32_t) * n);
+    std::memcpy(count, h.data() + P.dbg_count5, sizeof(int32_t) * 10 * n);
+    const double* m = at<const double>(h.data(), P.models5);   // [10][n][9] -> [n][10][9]
+    for (int i = 0; i < n; ++i)
+      for (int sidx = 0; sidx < 10; ++sidx)
+        std::memcpy(E + 9 * (10 * (size_t)i + sidx), m + 9 * ((size_t)sidx * n + i), sizeof(double) * 9);
   });
 }
 

@@ -20,6 +20,23 @@
 //                 the final masks and scores (fixed-order sums), the model
 //                 choice, the candidates, the depth vote (ballot counts), the
 //                 result record and the inlier mask.
+// Five-point mode (TvArgs::e5, BA_TV_E_FIVE_POINT) replaces the E half of the
+// first two stages and leaves the H half to the kernels above, instantiated
+// without their E work (E8 = false):
+//   k_tv_solve5   grid (pair, ceil(H / 64)), one lane per hypothesis.  The
+//                 10x20 system does not fit a lane's registers, and its
+//                 elimination indexes rows at run time; so the lane's system,
+//                 basis, derivative table and breakpoints live in its column
+//                 of an LDS array (236 doubles x 64 lanes = 118 KiB, one wave
+//                 per CU) and tv_solve_e5 (ba_two_view.h) is the very text a
+//                 host program runs.  Writes up to ten E per hypothesis into
+//                 slot s * H + h (solution-major) and their number.
+//   k_tv_score5   grid (pair, ceil(10 H / (64 / G5))): k_tv_score's E half
+//                 over the 10 H slots.  Solutions of high index are rare, so
+//                 in the solution-major order whole waves hold no live slot
+//                 and leave before the match loop.  Key: count << 32 |
+//                 (2^27 - 1 - h) << 4 | (15 - s): the larger count, then the
+//                 lower h, then the lower solution.
 // Every value a pair writes depends on its own data alone; there is no atomic
 // and no floating-point reduction whose order depends on the launch.
 #include <hip/hip_runtime.h>
@@ -55,6 +72,8 @@ __device__ __forceinline__ void tv_load_K(const float* K, double (&Kd)[9]) {
 }
 
 // D.n > 0: ba_two_view_hypotheses, hypotheses [D.h0, D.h0 + D.n) of pair D.pair into slots 0 .. D.n-1
+// E8 = false (five-point mode): the eight-point E is not formed (zeros, invalid)
+template <bool E8>
 __global__ __launch_bounds__(64) void k_tv_solve(TvArgs A, TvDebug D) {
   const bool dbg = D.n > 0;
   const int pair = dbg ? D.pair : (int)blockIdx.x;
@@ -80,7 +99,8 @@ __global__ __launch_bounds__(64) void k_tv_solve(TvArgs A, TvDebug D) {
     if (i < 4) { q1[i][0] = (double)m.x; q1[i][1] = (double)m.y; q2[i][0] = (double)m.z; q2[i][1] = (double)m.w; }
   }
   double E[9], Hm[9];
-  const bool ve = tv_solve_e(p1, p2, E);
+  bool ve = false;
+  if (E8) ve = tv_solve_e(p1, p2, E);
   const bool vh = tv_solve_h(q1, q2, Hm);
   double* o = A.models + 18 * slot;
 #pragma unroll
@@ -93,7 +113,7 @@ __global__ __launch_bounds__(64) void k_tv_solve(TvArgs A, TvDebug D) {
   }
 }
 
-template <bool DBG>
+template <bool DBG, bool E8>
 __global__ __launch_bounds__(64) void k_tv_score(TvArgs A, TvDebug D) {
   __shared__ float4 tile[kTvTile];
   const int lane = threadIdx.x;
@@ -117,7 +137,7 @@ __global__ __launch_bounds__(64) void k_tv_score(TvArgs A, TvDebug D) {
   if (live) {
     const size_t slot = DBG ? (size_t)idx : (size_t)pair * A.H + h;
     const double* mdl = A.models + 18 * slot;
-    ve = A.valid[2 * slot] != 0;
+    ve = E8 && A.valid[2 * slot] != 0;
     vh = A.valid[2 * slot + 1] != 0;
     double K1[9], K2[9], Ki1[9], Ki2[9], E[9];
     tv_load_K(A.K1 + 9 * (size_t)pair, K1);
@@ -126,7 +146,7 @@ __global__ __launch_bounds__(64) void k_tv_score(TvArgs A, TvDebug D) {
     p3p_inv3(K2, Ki2);
 #pragma unroll
     for (int e = 0; e < 9; ++e) { E[e] = mdl[e]; Hm[e] = mdl[9 + e]; }
-    tv_fundamental(E, Ki1, Ki2, F);
+    if (E8) tv_fundamental(E, Ki1, Ki2, F);
     if (vh) tv_inv3(Hm, Hi);
   }
   // ---- count both models over the pair's matches
@@ -139,9 +159,11 @@ __global__ __launch_bounds__(64) void k_tv_score(TvArgs A, TvDebug D) {
     for (int k = sub; k < m; k += G) {
       const float4 r = tile[k];
       const double u1 = (double)r.x, v1 = (double)r.y, u2 = (double)r.z, v2 = (double)r.w;
-      double d1, d2;
-      tv_e_dist2(F, u1, v1, u2, v2, &d1, &d2);
-      ce += (d1 <= A.thr2 && d2 <= A.thr2) ? 1 : 0;
+      if (E8) {
+        double d1, d2;
+        tv_e_dist2(F, u1, v1, u2, v2, &d1, &d2);
+        ce += (d1 <= A.thr2 && d2 <= A.thr2) ? 1 : 0;
+      }
       const double e2 = tv_h_err2(Hm, u1, v1, u2, v2), e1 = tv_h_err2(Hi, u2, v2, u1, v1);
       ch += (e1 <= A.thr2 && e2 <= A.thr2) ? 1 : 0;
     }
@@ -164,6 +186,105 @@ __global__ __launch_bounds__(64) void k_tv_score(TvArgs A, TvDebug D) {
   if (lane == 0) { rec[0] = me; rec[1] = mh; }
 }
 
+// ---------------------------------------------------------------------------
+// five-point mode
+// ---------------------------------------------------------------------------
+constexpr unsigned kTv5HKey = 0x07ffffffu;   // h < 2^16
+
+// D.n > 0: ba_two_view_hypotheses_e5 (models5 / nsol5 hold D.n hypotheses)
+__global__ __launch_bounds__(64) void k_tv_solve5(TvArgs A, TvDebug D) {
+  __shared__ double S[kTv5Store * 64];   // element i of lane l at S[64 i + l]
+  const bool dbg = D.n > 0;
+  const int pair = dbg ? D.pair : (int)blockIdx.x;
+  const int idx = (int)blockIdx.y * 64 + (int)threadIdx.x;
+  const int h = D.h0 + idx;
+  const int Hn = dbg ? D.n : A.H;
+  if (idx >= Hn) return;
+  const int o0 = A.off[pair], n = A.off[pair + 1] - o0;
+  if (n < A.n_min) return;   // FEW_POINTS: nothing reads the solutions
+  double K1[9], K2[9], Ki1[9], Ki2[9];
+  tv_load_K(A.K1 + 9 * (size_t)pair, K1);
+  tv_load_K(A.K2 + 9 * (size_t)pair, K2);
+  p3p_inv3(K1, Ki1);
+  p3p_inv3(K2, Ki2);
+  int smp[8];
+  tv_sample(A.seed, (uint32_t)h, n, smp);
+  double b1[5][2], b2[5][2];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const float4 m = A.m[(size_t)o0 + smp[i]];
+    tv_bearing(Ki1, (double)m.x, (double)m.y, b1[i]);
+    tv_bearing(Ki2, (double)m.z, (double)m.w, b2[i]);
+  }
+  const size_t base = dbg ? 0 : (size_t)pair * A.H;
+  double* out = A.models5 + 9 * (10 * base + (size_t)idx);
+  A.nsol5[base + idx] = tv_solve_e5(b1, b2, S + threadIdx.x, 64, out, 9 * (size_t)Hn);
+  if (dbg) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) D.sample[8 * (size_t)idx + i] = smp[i];
+  }
+}
+
+template <bool DBG>
+__global__ __launch_bounds__(64) void k_tv_score5(TvArgs A, TvDebug D) {
+  __shared__ float4 tile[kTvTile];
+  const int lane = threadIdx.x;
+  const int pair = DBG ? D.pair : (int)blockIdx.x;
+  const int G = DBG ? 1 : A.G5, hpw = 64 / G, sub = lane & (G - 1);
+  const int Hn = DBG ? D.n : A.H;
+  const int q = (int)blockIdx.y * hpw + lane / G;   // slot s * Hn + i
+  const bool inr = q < 10 * Hn;
+  const int sol = inr ? q / Hn : 0, idx = inr ? q - sol * Hn : 0;
+  const int h = DBG ? D.h0 + idx : idx;
+  const int nw = (10 * A.H + hpw - 1) / hpw;
+  unsigned long long* rec = DBG ? nullptr : A.rec5 + ((size_t)pair * nw + blockIdx.y);
+  const int o0 = A.off[pair], n = A.off[pair + 1] - o0;
+  const size_t base = DBG ? 0 : (size_t)pair * A.H;
+  const bool live = n >= A.n_min && inr && sol < A.nsol5[base + idx];
+  if (__ballot(live) == 0ull) {   // FEW_POINTS, or no solution in any of the wave's slots
+    if (!DBG && lane == 0) rec[0] = 0ull;
+    if (DBG && inr) D.count5[10 * (size_t)idx + sol] = 0;
+    return;
+  }
+  double F[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) F[e] = 0.0;
+  if (live) {
+    const double* mdl = A.models5 + 9 * (10 * base + (size_t)q);
+    double K1[9], K2[9], Ki1[9], Ki2[9], E[9];
+    tv_load_K(A.K1 + 9 * (size_t)pair, K1);
+    tv_load_K(A.K2 + 9 * (size_t)pair, K2);
+    p3p_inv3(K1, Ki1);
+    p3p_inv3(K2, Ki2);
+#pragma unroll
+    for (int e = 0; e < 9; ++e) E[e] = mdl[e];
+    tv_fundamental(E, Ki1, Ki2, F);
+  }
+  int ce = 0;
+  for (int b0 = 0; b0 < n; b0 += kTvTile) {
+    const int m = min(kTvTile, n - b0);
+    __syncthreads();
+    for (int k = lane; k < m; k += 64) tile[k] = A.m[(size_t)o0 + b0 + k];
+    __syncthreads();
+    for (int k = sub; k < m; k += G) {
+      const float4 r = tile[k];
+      double d1, d2;
+      tv_e_dist2(F, (double)r.x, (double)r.y, (double)r.z, (double)r.w, &d1, &d2);
+      ce += (d1 <= A.thr2 && d2 <= A.thr2) ? 1 : 0;
+    }
+  }
+  for (int off = 1; off < G; off <<= 1) ce += __shfl_xor(ce, off, 64);
+  if (!live) ce = 0;
+  if (DBG) {
+    if (inr) D.count5[10 * (size_t)idx + sol] = ce;
+    return;
+  }
+  // ties: the lower h, then the lower solution; key 0: no solution
+  const unsigned long long lo = ((unsigned long long)(kTv5HKey - (unsigned)h) << 4) | (unsigned long long)(15 - sol);
+  const unsigned long long me = tv_wave_max(live ? ((unsigned long long)(unsigned)ce << 32) | lo : 0ull);
+  if (lane == 0) rec[0] = me;
+}
+
 __global__ __launch_bounds__(64) void k_tv_select(TvArgs A) {
   const int pair = blockIdx.x, lane = threadIdx.x;
   const int o0 = A.off[pair], n = A.off[pair + 1] - o0;
@@ -181,11 +302,22 @@ __global__ __launch_bounds__(64) void k_tv_select(TvArgs A) {
       ke = a > ke ? a : ke;
       kh = b > kh ? b : kh;
     }
+    if (A.e5) {   // the E key comes from the five-point slots
+      const int hpw5 = 64 / A.G5, nw5 = (10 * A.H + hpw5 - 1) / hpw5;
+      const unsigned long long* rec5 = A.rec5 + (size_t)pair * nw5;
+      ke = 0ull;
+      for (int w = lane; w < nw5; w += 64) {
+        const unsigned long long a = rec5[w];
+        ke = a > ke ? a : ke;
+      }
+    }
     ke = tv_wave_max(ke);
     kh = tv_wave_max(kh);
   }
   const int votes_e = (int)(ke >> 32), votes_h = (int)(kh >> 32);
-  const int he = ke ? (int)(0x7fffffffu - (unsigned)(ke & 0xffffffffull)) : -1;
+  const int sol_e = A.e5 && ke ? 15 - (int)(ke & 15ull) : 0;
+  const int he = A.e5 ? (ke ? (int)(kTv5HKey - (unsigned)((ke & 0xffffffffull) >> 4)) : -1)
+                      : ke ? (int)(0x7fffffffu - (unsigned)(ke & 0xffffffffull)) : -1;
   const int hh = kh ? (int)(0x7fffffffu - (unsigned)(kh & 0xffffffffull)) : -1;
   bool avail_e = ke != 0ull && votes_e >= A.inl_min, avail_h = kh != 0ull && votes_h >= A.inl_min;
 
@@ -200,7 +332,7 @@ __global__ __launch_bounds__(64) void k_tv_select(TvArgs A) {
     p3p_inv3(K1, Ki1);
     p3p_inv3(K2, Ki2);
     if (avail_e) {
-      const double* mdl = A.models + 18 * ((size_t)pair * A.H + he);
+      const double* mdl = A.e5 ? A.models5 + 9 * ((10 * (size_t)pair + sol_e) * A.H + he) : A.models + 18 * ((size_t)pair * A.H + he);
       double E[9];
 #pragma unroll
       for (int e = 0; e < 9; ++e) E[e] = mdl[e];
@@ -326,21 +458,36 @@ __global__ __launch_bounds__(64) void k_tv_select(TvArgs A) {
     for (int e = 0; e < 6; ++e) res[29 + e] = cam[e];
 #pragma unroll
     for (int e = 0; e < 3; ++e) res[35 + e] = nrm[e];
+    res[38] = ok && avail_e ? sol_e : 0;
   }
 }
 
 void launch_two_view(const TvArgs& A, hipStream_t s) {
   if (A.n_pair <= 0) return;
   const int hpw = 64 / A.G, nw = (A.H + hpw - 1) / hpw;
-  hipLaunchKernelGGL(k_tv_solve, dim3(A.n_pair, (A.H + 63) / 64), dim3(64), 0, s, A, TvDebug{});
-  hipLaunchKernelGGL(k_tv_score<false>, dim3(A.n_pair, nw), dim3(64), 0, s, A, TvDebug{});
+  if (A.e5) {
+    const int hpw5 = 64 / A.G5, nw5 = (10 * A.H + hpw5 - 1) / hpw5;
+    hipLaunchKernelGGL(k_tv_solve<false>, dim3(A.n_pair, (A.H + 63) / 64), dim3(64), 0, s, A, TvDebug{});
+    hipLaunchKernelGGL(k_tv_solve5, dim3(A.n_pair, (A.H + 63) / 64), dim3(64), 0, s, A, TvDebug{});
+    hipLaunchKernelGGL((k_tv_score<false, false>), dim3(A.n_pair, nw), dim3(64), 0, s, A, TvDebug{});
+    hipLaunchKernelGGL(k_tv_score5<false>, dim3(A.n_pair, nw5), dim3(64), 0, s, A, TvDebug{});
+  } else {
+    hipLaunchKernelGGL(k_tv_solve<true>, dim3(A.n_pair, (A.H + 63) / 64), dim3(64), 0, s, A, TvDebug{});
+    hipLaunchKernelGGL((k_tv_score<false, true>), dim3(A.n_pair, nw), dim3(64), 0, s, A, TvDebug{});
+  }
   hipLaunchKernelGGL(k_tv_select, dim3(A.n_pair), dim3(64), 0, s, A);
 }
 
 void launch_two_view_hypotheses(const TvArgs& A, const TvDebug& D, hipStream_t s) {
   if (D.n <= 0) return;
-  hipLaunchKernelGGL(k_tv_solve, dim3(1, (D.n + 63) / 64), dim3(64), 0, s, A, D);
-  hipLaunchKernelGGL(k_tv_score<true>, dim3(1, (D.n + 63) / 64), dim3(64), 0, s, A, D);
+  hipLaunchKernelGGL(k_tv_solve<true>, dim3(1, (D.n + 63) / 64), dim3(64), 0, s, A, D);
+  hipLaunchKernelGGL((k_tv_score<true, true>), dim3(1, (D.n + 63) / 64), dim3(64), 0, s, A, D);
+}
+
+void launch_two_view_hypotheses_e5(const TvArgs& A, const TvDebug& D, hipStream_t s) {
+  if (D.n <= 0) return;
+  hipLaunchKernelGGL(k_tv_solve5, dim3(1, (D.n + 63) / 64), dim3(64), 0, s, A, D);
+  hipLaunchKernelGGL(k_tv_score5<true>, dim3(1, (10 * D.n + 63) / 64), dim3(64), 0, s, A, D);
 }
 
 }  // namespace bahip

@@ -147,6 +147,8 @@ inline ba_two_view_options check_two_view(const char* fn, const ba_two_view_batc
   if (p.min_good < 0) throw invalid("min_good " + std::to_string(p.min_good) + " is negative");
   if (p.model != BA_TV_AUTO && p.model != BA_TV_ESSENTIAL && p.model != BA_TV_HOMOGRAPHY)
     throw invalid("unknown model " + std::to_string(p.model));
+  if (p.reserved != BA_TV_E_EIGHT_POINT && p.reserved != BA_TV_E_FIVE_POINT)
+    throw invalid("unknown e_solver " + std::to_string(p.reserved));
   if (!(p.threshold_px > 0.0 && p.threshold_px <= 1.7976931348623157e308))
     throw invalid("threshold_px must be positive and finite");
   if (!(p.h_ratio >= 0.0 && p.h_ratio <= 1.0)) throw invalid("h_ratio must lie in [0, 1]");
@@ -158,23 +160,34 @@ inline ba_two_view_options check_two_view(const char* fn, const ba_two_view_batc
   return p;
 }
 
-// The staging buffer of the two entries.  ba_two_view_ransac (dbg_n == 0):
+// The staging buffer of the entries.  ba_two_view_ransac (dbg_n == 0):
 // offsets, K1, K2, matches as (u1, v1, u2, v2) | result records, inlier mask |
-// models, validity, wave records.  ba_two_view_hypotheses (dbg_n > 0): the
-// batch | samples, models, validity, counts of the dbg_n hypotheses.
+// models, validity, wave records and, in five-point mode only (e5), the
+// solutions (720 B per hypothesis), their counts per hypothesis and the wave
+// records of their vote.  ba_two_view_hypotheses (dbg_n > 0): the batch |
+// samples, models, validity, counts of the dbg_n hypotheses;
+// ba_two_view_hypotheses_e5 (dbg_n > 0, e5): the batch | samples, solution
+// counts, solutions, votes.
 struct TwoViewLayout {
   SectionLayout L{256};
   size_t off = 0, K1 = 0, K2 = 0, m = 0;
   size_t res = 0, inlier = 0;
   size_t models = 0, valid = 0, rec = 0;
-  size_t dbg_sample = 0, dbg_count = 0;
+  size_t models5 = 0, nsol5 = 0, rec5 = 0;
+  size_t dbg_sample = 0, dbg_count = 0, dbg_count5 = 0;
 };
-inline TwoViewLayout two_view_layout(size_t N, size_t NM, int H, int G, size_t dbg_n) {
+inline TwoViewLayout two_view_layout(size_t N, size_t NM, int H, int G, size_t dbg_n, bool e5 = false, int G5 = 1) {
   TwoViewLayout P;
   SectionLayout& L = P.L;
   P.off = L.add(sizeof(int32_t) * (N + 1)); P.K1 = L.add(sizeof(float) * 9 * N); P.K2 = L.add(sizeof(float) * 9 * N);
   P.m = L.add(sizeof(float) * 4 * NM);
   L.end_inputs();
+  if (dbg_n > 0 && e5) {
+    P.dbg_sample = L.add(sizeof(int32_t) * 8 * dbg_n); P.nsol5 = L.add(sizeof(int32_t) * dbg_n);
+    P.models5 = L.add(sizeof(double) * 90 * dbg_n); P.dbg_count5 = L.add(sizeof(int32_t) * 10 * dbg_n);
+    L.end_outputs();
+    return P;
+  }
   if (dbg_n > 0) {
     P.dbg_sample = L.add(sizeof(int32_t) * 8 * dbg_n); P.models = L.add(sizeof(double) * 18 * dbg_n);
     P.valid = L.add(sizeof(int32_t) * 2 * dbg_n); P.dbg_count = L.add(sizeof(int32_t) * 2 * dbg_n);
@@ -186,6 +199,11 @@ inline TwoViewLayout two_view_layout(size_t N, size_t NM, int H, int G, size_t d
   const size_t hpw = 64 / (size_t)G, nw = ((size_t)H + hpw - 1) / hpw;
   P.models = L.add(sizeof(double) * 18 * (size_t)H * N); P.valid = L.add(sizeof(int32_t) * 2 * (size_t)H * N);
   P.rec = L.add(sizeof(uint64_t) * 2 * nw * N);
+  if (e5) {
+    const size_t hpw5 = 64 / (size_t)G5, nw5 = (10 * (size_t)H + hpw5 - 1) / hpw5;
+    P.models5 = L.add(sizeof(double) * 90 * (size_t)H * N); P.nsol5 = L.add(sizeof(int32_t) * (size_t)H * N);
+    P.rec5 = L.add(sizeof(uint64_t) * nw5 * N);
+  }
   return P;
 }
 // The matches of a batch as the kernels read them: (u1, v1, u2, v2) per match

@@ -89,7 +89,9 @@ class PnpResult:
 @dataclass
 class TwoViewResult:
     """ba_two_view_result: status is an N.TV_* code, model N.TV_ESSENTIAL or
-    N.TV_HOMOGRAPHY; cam = [w, t] maps frame 1 to frame 2."""
+    N.TV_HOMOGRAPHY; cam = [w, t] maps frame 1 to frame 2.  best_solution_e
+    (the C struct's `reserved`): with e_solver = N.TV_E_FIVE_POINT the index
+    of the winning solution within best_hypothesis_e, else 0."""
     status: int
     model: int
     n_inliers: int
@@ -105,6 +107,7 @@ class TwoViewResult:
     H: np.ndarray
     cam: np.ndarray
     normal: np.ndarray
+    best_solution_e: int = 0
 
 
 ITER_FIELDS = [f for f, _ in N.ba_iteration._fields_]
@@ -629,6 +632,9 @@ class Solver:
         p = N.ba_two_view_options()
         self.lib.ba_two_view_defaults(C.byref(p))
         for key, val in tv_options.items():
+            if key == "e_solver":                       # the C member keeps the name `reserved`
+                p.reserved = int(val)
+                continue
             if key not in TV_OPTION_FIELDS:
                 raise TypeError(f"two_view: unknown option {key!r}")
             setattr(p, key, float(val) if key in ("threshold_px", "h_ratio") else int(val))
@@ -641,7 +647,8 @@ class Solver:
         positive-depth vote.  Pair i owns matches match_offset[i] ..
         match_offset[i+1]; K1 / K2 (n, 9) col-major (K2 None: K1); uv1 / uv2
         (n_matches, 2) float32 pixels.  tv_options: max_hypotheses,
-        min_points, min_inliers, min_good, model, seed, threshold_px, h_ratio
+        min_points, min_inliers, min_good, model, seed, threshold_px, h_ratio,
+        e_solver (N.TV_E_EIGHT_POINT, the default, or N.TV_E_FIVE_POINT)
         (defaults: ba_two_view_defaults).  Returns (inlier mask (n_matches,)
         bool, results)."""
         b, p, n, nm, _keep = self._two_view_batch(match_offset, K1, K2, uv1, uv2, tv_options)
@@ -651,7 +658,7 @@ class Solver:
         results = [TwoViewResult(r.status, r.model, r.n_inliers, r.n_good, r.n_good_second, r.best_hypothesis_e,
                                  r.best_hypothesis_h, r.votes_e, r.votes_h, r.score_e, r.score_h,
                                  np.array(r.E[:]).reshape(3, 3), np.array(r.H[:]).reshape(3, 3), np.array(r.cam[:]),
-                                 np.array(r.normal[:])) for r in list(res)[:n]]
+                                 np.array(r.normal[:]), r.reserved) for r in list(res)[:n]]
         return inl.astype(bool), results
 
     def two_view_hypotheses(self, match_offset, K1, K2, uv1, uv2, pair: int, h0: int, n: int, **tv_options) -> dict:
@@ -669,6 +676,23 @@ class Solver:
                                                     _ptr(sample), _ptr(E), _ptr(H), _ptr(valid), _ptr(count)),
                     "ba_two_view_hypotheses")
         return {"sample": sample, "E": E, "H": H, "valid": valid, "count": count}
+
+    def two_view_hypotheses_e5(self, match_offset, K1, K2, uv1, uv2, pair: int, h0: int, n: int, **tv_options) -> dict:
+        """Hypotheses h0 .. h0+n-1 of one pair exactly as two_view_ransac forms
+        and scores them with e_solver = N.TV_E_FIVE_POINT
+        (ba_two_view_hypotheses_e5): sample (n, 8) local match indices (the
+        first five are used), n_sol (n,), E (n, 10, 3, 3) with zeros past
+        n_sol, count (n, 10)."""
+        b, p, _n, _nm, _keep = self._two_view_batch(match_offset, K1, K2, uv1, uv2, tv_options)
+        m = max(int(n), 0)
+        sample = np.zeros((m, 8), np.int32)
+        n_sol = np.zeros(m, np.int32)
+        E = np.zeros((m, 10, 3, 3))
+        count = np.zeros((m, 10), np.int32)
+        self._check(self.lib.ba_two_view_hypotheses_e5(self.h, C.byref(b), C.byref(p), int(pair), int(h0), int(n),
+                                                       _ptr(sample), _ptr(n_sol), _ptr(E), _ptr(count)),
+                    "ba_two_view_hypotheses_e5")
+        return {"sample": sample, "n_sol": n_sol, "E": E, "count": count}
 
     def two_view_times(self) -> np.ndarray:
         """Times (ms) of the last two_view_ransac: host preparation (wall), the

@@ -642,6 +642,61 @@ int ba_pnp_hypotheses(ba_ctx* ctx, const ba_pose_batch* batch, const ba_pnp_opti
  * the reference's pose is its inverse.  No refit follows: callers refine with
  * ba_triangulate and the window BA.
  *
+ * The five-point essential solver (e_solver = BA_TV_E_FIVE_POINT; opt-in: with
+ * BA_TV_E_EIGHT_POINT, the default, every output bit is what it was before
+ * the selector existed).  cv::findEssentialMat is a five-point RANSAC: a
+ * hypothesis is an essential matrix by construction, so the projection after
+ * the vote changes the winner at rounding level only.  The sampler, the
+ * homography hypotheses and everything after the vote are untouched: H,
+ * votes_h, best_hypothesis_h and score_h are bitwise those of the eight-point
+ * mode.  Per hypothesis (csrc/ba_two_view.h, tv_solve_e5):
+ *   Sample: the first five of the eight picks.
+ *   Null space: rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1] of the
+ *     dehomogenised bearings; X, Y, Z, W = H_0 .. H_4 e_j, j = 5 .. 8, of the
+ *     Householder QR of the transposed 5x9 system (orthonormal whatever the
+ *     rank).  E = xX + yY + zZ + W.
+ *   Constraints: a 10x20 matrix; rows 0 .. 8 are the entries of 2 E E^T E -
+ *     tr(E E^T) E, row-major, row 9 is det E (cofactors of the first row).
+ *     Columns (Nister's order, the first ten are eliminated):
+ *       x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1.
+ *   Elimination: Gauss-Jordan on the first ten columns with partial pivoting
+ *     (the largest |entry| of the column at or below the diagonal, ties to
+ *     the lower row).  A pivot at or below 1e-13 times the largest |entry| of
+ *     the matrix ends the elimination without solutions.  Only rows 4 .. 9 are
+ *     read afterwards (rows 0 .. 3 are not reduced further once pivoted).
+ *   Hidden variable: the elimination is run for the three turns of the basis
+ *     ((x, y, z) on (X, Y, Z), (Y, Z, X), (Z, X, Y)); the turn whose reduced
+ *     rows 4 .. 9 have the smallest largest |entry| is kept (ties: the
+ *     earlier): the cancellation in the determinant below grows with those
+ *     entries.  No turn eliminated: no solutions.
+ *   Polynomial: <k> = row 4 - z row 5, <l> = row 6 - z row 7, <m> = row 8 -
+ *     z row 9 are x px(z) + y py(z) + p1(z) of degrees 3, 3, 4; the
+ *     tenth-degree polynomial p is the determinant of the 3x3 matrix
+ *     [px py p1], expanded by its third column, scaled by its largest
+ *     |coefficient|.
+ *   Roots: all real roots in [-B, B], B = min(1e25, Fujiwara's bound
+ *     2 max_k |p_(10-k) / p_10|^(1/k)).  For d = 1 .. 10 the roots of the
+ *     (10 - d)-th derivative are sought between the roots of the derivative
+ *     before (and -B, B), where the polynomial is monotonic: a sign change
+ *     (v < 0 against v >= 0, by Horner; for d = 10 the 3x3 determinant
+ *     itself is evaluated at z instead of its expansion) brackets the one
+ *     root, found by at most 64 bisections on the ordered integers of the
+ *     doubles (to adjacent doubles; the end with the smaller |v|); an interval
+ *     without a sign change hands its upper end on as a placeholder.  There is
+ *     no recursion, and every loop has a fixed cap: 10 levels, at most 10
+ *     intervals each, 64 bisections, 12 polishing steps.
+ *   Back-substitution: (x, y, 1) is the cross product of the two rows of
+ *     [px py p1](z) whose third component is the largest in magnitude (ties:
+ *     (0,1), (0,2), (1,2)).  Then (x, y, z) takes Gauss-Newton steps on the
+ *     nine cubic constraints, cost |C(E)|^2 / |E|^6: at most 12, ending at a
+ *     cost <= 1e-30 or at the first step that does not lower the cost.
+ *   Solutions: E scaled to Frobenius norm 1 (either sign); a non-finite one is
+ *     dropped; order: increasing root of the hidden variable.  Up to ten.
+ *   Vote: every (hypothesis, solution) is scored by the E predicate above
+ *     over all matches.  The largest count wins; ties go to the lower h, then
+ *     to the lower solution index.  best_solution (the result's `reserved`)
+ *     is the winner's index within its hypothesis.
+ *
  * Statuses: fewer than max(8, min_points) matches is BA_TV_FEW_POINTS.  Every
  * failure returns cam = 0, normal = 0, n_inliers = 0, inlier all 0 and both
  * best_hypothesis fields -1; FEW_POINTS and NO_MODEL zero the rest of the
@@ -659,12 +714,14 @@ int ba_pnp_hypotheses(ba_ctx* ctx, const ba_pose_batch* batch, const ba_pnp_opti
  *                            match_offset[0] != 0 or a decreasing match_offset
  *                            (the message names the pair), max_hypotheses
  *                            outside 1 .. 65536, negative min_points /
- *                            min_inliers / min_good, an unknown model, a
+ *                            min_inliers / min_good, an unknown model, an
+ *                            unknown e_solver (the field `reserved`), a
  *                            threshold_px that is not positive and finite, an
  *                            h_ratio outside [0, 1],
  *   BA_ERR_OUT_OF_MEMORY     the scratch cannot be allocated. */
 enum ba_tv_status { BA_TV_OK = 0, BA_TV_FEW_POINTS = 1, BA_TV_NO_MODEL = 2, BA_TV_NO_POSE = 3 };
 enum ba_tv_model  { BA_TV_AUTO = 0, BA_TV_ESSENTIAL = 1, BA_TV_HOMOGRAPHY = 2 };
+enum ba_tv_e_solver { BA_TV_E_EIGHT_POINT = 0, BA_TV_E_FIVE_POINT = 1 };
 
 typedef struct {            /* pair i owns matches [match_offset[i], match_offset[i+1]) */
   int32_t n_pairs, reserved;
@@ -681,7 +738,7 @@ typedef struct {
   int32_t min_inliers;     /* default 8: a winner's vote below max(8, min_inliers) is NO_MODEL */
   int32_t min_good;        /* default 101: the reference's `inliers <= 100 -> false` (SfMHelper.cpp:656) */
   int32_t model;           /* default BA_TV_AUTO */
-  int32_t reserved;
+  int32_t reserved;        /* the E solver, enum ba_tv_e_solver: default BA_TV_E_EIGHT_POINT (0); the member keeps its name */
   uint64_t seed;           /* default 0 */
   double  threshold_px;    /* default 1.0: the reference's RANSAC thresholds (lines 532, 536) */
   double  h_ratio;         /* default 0.4 (line 643) */
@@ -693,7 +750,8 @@ typedef struct {
   int32_t n_good, n_good_second;       /* positive-depth votes: best and runner-up candidate */
   int32_t best_hypothesis_e, best_hypothesis_h;   /* -1 without a model */
   int32_t votes_e, votes_h;            /* the winners' RANSAC votes */
-  int32_t reserved;
+  int32_t reserved;                    /* five-point: the winning solution's index within best_hypothesis_e; 0 in
+                                          eight-point mode and whenever best_hypothesis_e is -1 */
   double  score_e, score_h;            /* S_E, S_H */
   double  E[9], H[9];                  /* row-major, Frobenius norm 1; E after the essential projection */
   double  cam[6];                      /* [w, t]: frame 1 -> frame 2 (x2 ~ R x1 + t), |t| = 1, ceres angle-axis */
@@ -710,11 +768,23 @@ int ba_two_view_times(ba_ctx* ctx, double* ms, int n);
  * max_hypotheses) of pair `pair` exactly as ba_two_view_ransac forms and
  * scores them (min_points is not applied; the pair needs 8 matches).  sample:
  * the eight local match indices; E, H: the models, row-major (zeros when
- * invalid); valid and count: (E, H) per hypothesis.  Same errors as
+ * invalid), E the eight-point one whatever the selector; valid and count:
+ * (E, H) per hypothesis.  Same errors as
  * ba_two_view_ransac, plus a pair or hypothesis range out of bounds. */
 int ba_two_view_hypotheses(ba_ctx* ctx, const ba_two_view_batch* batch, const ba_two_view_options* opt, int pair, int h0,
                            int n, int32_t* sample /* [8*n] */, double* E /* [9*n] */, double* H /* [9*n] */,
                            int32_t* valid /* [2*n]: E, H */, int32_t* count /* [2*n] */);
+/* Test / inspection entry point of the five-point solver, on the model of
+ * ba_pnp_hypotheses: hypotheses h0 .. h0+n-1 of pair `pair` exactly as
+ * ba_two_view_ransac forms and scores them with e_solver =
+ * BA_TV_E_FIVE_POINT (whatever opt's selector says).  sample: the eight local
+ * match indices (the first five are used); n_sol: 0 .. 10; E: the solutions
+ * in their fixed order, row-major, Frobenius norm 1 (unused entries zero);
+ * count: their votes at threshold_px (0 past n_sol).  Same errors as
+ * ba_two_view_hypotheses. */
+int ba_two_view_hypotheses_e5(ba_ctx* ctx, const ba_two_view_batch* batch, const ba_two_view_options* opt, int pair, int h0,
+                              int n, int32_t* sample /* [8*n] */, int32_t* n_sol /* [n] */, double* E /* [n][10][9] */,
+                              int32_t* count /* [n][10] */);
 
 /* Test / inspection entry point: the state inside ceres::Solve's
  * SchurComplementSolver (Optimizer.cpp:242, DENSE_SCHUR) for one step.

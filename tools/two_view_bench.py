@@ -9,7 +9,9 @@ Every figure is the median of --reps timed calls after --warmup calls: wall
 time (host clock around the blocking call) and the kernels' device time (HIP
 events) beside it, then picoseconds per (hypothesis x match), where one unit
 is both models' predicates on one match.  The numbers are reported, not
-gated.  Each shape runs in a child process of its own under `timeout -k 10`;
+gated.  --e-solver picks the essential solver: eight (the default) or five
+(the five-point solver, every real root scored; a unit is then still one
+hypothesis x match, whatever the number of roots).  Each shape runs in a child process of its own under `timeout -k 10`;
 the first shape that fails ends the run.  Writes one JSON record (default
 profiles/two_view_bench.json) and prints it.
 """
@@ -68,7 +70,8 @@ def child(a, pairs):
     with Solver(0) as s:
         for it in range(a.warmup + a.reps):
             t0 = time.perf_counter()
-            inl, res = s.two_view_ransac(off, K, None, uv1, uv2, max_hypotheses=a.hypotheses)
+            inl, res = s.two_view_ransac(off, K, None, uv1, uv2, max_hypotheses=a.hypotheses,
+                                         e_solver=N.TV_E_FIVE_POINT if a.e_solver == "five" else N.TV_E_EIGHT_POINT)
             if it >= a.warmup:
                 wall.append(1e3 * (time.perf_counter() - t0))
                 kern.append(s.two_view_times())
@@ -76,7 +79,10 @@ def child(a, pairs):
     rot = [float(np.linalg.norm(rotation_to_angle_axis((angle_axis_to_rotation(r.cam[:3]) @ sc[i][0].T)[None])[0]))
            for i, r in enumerate(res) if r.status == N.TV_OK]
     units = pairs * a.hypotheses * a.matches
-    rec = {"pairs": pairs, "matches": a.matches, "hypotheses": a.hypotheses, "outlier_fraction": a.outliers,
+    # the census of section 21.4: the share of the E winner's votes that its essential projection keeps
+    kept = [r.n_inliers / r.votes_e for r in res if r.status == N.TV_OK and r.model == N.TV_ESSENTIAL and r.votes_e > 0]
+    general_as_h = sum(r.model == N.TV_HOMOGRAPHY for i, r in enumerate(res) if not i & 1)
+    rec = {"pairs": pairs, "e_solver": a.e_solver, "matches": a.matches, "hypotheses": a.hypotheses, "outlier_fraction": a.outliers,
            "wall_ms": statistics.median(wall), "wall_ms_min": min(wall), "wall_ms_max": max(wall),
            "host_prep_ms": float(np.median(k[:, 0])), "kernel_ms": float(np.median(k[:, 1])),
            "wall_ps_per_hypothesis_match": 1e9 * statistics.median(wall) / units,
@@ -86,6 +92,9 @@ def child(a, pairs):
            "model_counts": {"ESSENTIAL": sum(r.model == N.TV_ESSENTIAL for r in res),
                             "HOMOGRAPHY": sum(r.model == N.TV_HOMOGRAPHY for r in res)},
            "expected_models": {"ESSENTIAL": (pairs + 1) // 2, "HOMOGRAPHY": pairs // 2},
+           "general_scenes_scored_as_homographies": int(general_as_h),
+           "votes_kept_by_projection": {"pairs": len(kept), "min": min(kept) if kept else None,
+                                        "mean": float(np.mean(kept)) if kept else None},
            "inliers_mean": float(np.mean([r.n_inliers for r in res])),
            "rotation_error_rad_max": max(rot) if rot else None}
     print(json.dumps(rec))
@@ -99,6 +108,7 @@ def main():
     ap.add_argument("--hypotheses", type=int, default=1000)
     ap.add_argument("--pairs", type=int, default=256)
     ap.add_argument("--outliers", type=float, default=0.3)
+    ap.add_argument("--e-solver", choices=("eight", "five"), default="eight")
     ap.add_argument("--step-timeout", type=int, default=120, help="seconds per shape")
     ap.add_argument("--tree", default="", help="a label of the source tree, recorded as given")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "two_view_bench.json"))
@@ -107,13 +117,13 @@ def main():
     if a.child:
         child(a, a.child)
         return 0
-    rec = {"date": time.strftime("%Y-%m-%d"), "tree": a.tree, "reps": a.reps, "warmup": a.warmup,
+    rec = {"date": time.strftime("%Y-%m-%d"), "tree": a.tree, "e_solver": a.e_solver, "reps": a.reps, "warmup": a.warmup,
            "pnp_kernel_ps_per_hypothesis_point": {"one_frame": 116.0, "many_frames": 7.8}}
     rc = 0
     for name, pairs in (("one_pair", 1), ("many_pairs", a.pairs)):
         cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, __file__, "--child", str(pairs),
                "--reps", str(a.reps), "--warmup", str(a.warmup), "--matches", str(a.matches),
-               "--hypotheses", str(a.hypotheses), "--outliers", str(a.outliers)]
+               "--hypotheses", str(a.hypotheses), "--outliers", str(a.outliers), "--e-solver", a.e_solver]
         p = subprocess.run(cmd, capture_output=True, text=True)
         if p.returncode != 0:      # a fault, an abort or the time limit: nothing more is started
             rec[name] = {"exit_status": p.returncode, "stderr_tail": p.stderr[-2000:]}
