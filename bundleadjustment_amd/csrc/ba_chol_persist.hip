@@ -163,8 +163,6 @@ __device__ inline void tile_put_masked(double (*D)[LDP], const TileRegs& t, int 
 struct OvArgs {
   int on = 0;
   int pass_only = 0;         // (diagnostics, ba_debug_blocks: every workgroup only takes items; no factorisation)
-  int worker_items = 0;      // (diagnostics, BA_OV_WORKERS: 0 items between updates, 2 none)
-  int far = kOvFar;          // (BA_OV_FAR: the distance from its last update below which a worker takes no item)
   DevProblem P;
   const int4* blocks;
   const int2* pairs;
@@ -181,7 +179,6 @@ struct OvArgs {
   // blocks {I, J, start, end} (no block: zeros), or a diagonal item's
   // {-1 - (v G + g), 0, 0, 0} first
   const int4* irec;
-  const int* item_col;       // the tile column each item belongs to
   const unsigned* tgt;       // [TR][T] contributions per tile and launch
   unsigned* cnt;             // [TR][T] contributions (cumulative)
   unsigned* cam_cnt;         // [nvc] slices done (cumulative)
@@ -822,18 +819,18 @@ __global__ __launch_bounds__(256) void k_chol_persist(PersistArgs a) {
       if (!diag) tile_put(S1, tJ);
     };
     __shared__ int ov_sh[2];   // (overlapped form: update k ready | the queue is empty)
-    bool no_items = !ov.on || ov.worker_items != 0;
+    bool no_items = !ov.on;
     if (threadIdx.x == 0) ov_sh[1] = 0;
     auto up = [&](const unsigned* f) {
       return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.epoch;
     };
     bool staged = false;
-    if (kmax >= 0 && (no_items || J < ov.far)) {
+    if (kmax >= 0 && (no_items || J < kOvFar)) {
       stage_panels(0);
       staged = true;
     }
     for (int k = 0; k <= kmax;) {
-      if (!no_items && J - k >= ov.far) {
+      if (!no_items && J - k >= kOvFar) {
         if (threadIdx.x == 0) {
           bool r = up(&vflag[k]);
           if (r) r = k >= 1 ? up(&tflag[I * T + k]) && (diag || up(&tflag[J * T + k]))
@@ -922,7 +919,7 @@ __global__ __launch_bounds__(256) void k_chol_persist(PersistArgs a) {
       if (stamp && k == kmax) WSTAMP(J, 3);
       ++k;
       staged = false;
-      if (k <= kmax && (no_items || J - k < ov.far)) {
+      if (k <= kmax && (no_items || J - k < kOvFar)) {
         stage_panels(k);
         staged = true;
       }
@@ -1010,15 +1007,11 @@ void launch_chol_persist_ov(const DevProblem& P, const DevWork& W, OvPlan& plan,
   OvArgs& o = a.ov;
   o.on = 1;
   o.pass_only = pass_only ? 1 : 0;
-  const char* we = getenv("BA_OV_WORKERS");
-  o.worker_items = we ? atoi(we) : 0;
-  const char* fe = getenv("BA_OV_FAR");
-  o.far = fe && atoi(fe) > 0 ? atoi(fe) : kOvFar;
   o.P = P;
   o.blocks = W.blocks; o.pairs = W.pairs; o.Wc = W.W; o.scale_c = W.scale_c; o.u = W.u;
   o.Hcc = W.Hcc; o.gc = W.gc; o.diag_c = W.diag_c; o.radius = radius;
   o.cpart = W.cpart; o.G = W.cam_split;
-  o.irec = plan.irec; o.item_col = plan.item_col; o.tgt = plan.tgt;
+  o.irec = plan.irec; o.tgt = plan.tgt;
   o.cnt = plan.ctr;
   o.cam_cnt = plan.ctr + (size_t)TR * T;
   o.q = o.cam_cnt + P.nvc;

@@ -5,13 +5,23 @@
 //                   launch, a chain workgroup for the diagonal blocks and the
 //                   tile tasks, synchronised by epoch-tagged flags;
 //   fused           per block step, k_chol_upd: the critical workgroup and the
-//                   step's tile tasks, whose column tasks form the next panel;
-//   panels          the same with k_chol_panel launches (BA_CHOL_FUSE=0);
-// and the round-5 rank-64 form (k_chol_step_split, BA_CHOL_RANK=0), where
-// every trailing tile takes every panel.  DESIGN.md section 15.2.  Its own
-// translation unit, so the fused step of ba_chol.hip keeps its code
-// generation (a shared template changed the inlining of the critical
-// workgroup's factor_invert_blk; here the calls force it inline).
+//                   step's tile tasks, whose column tasks form the next panel
+//                   (BA_CHOL_FLOW=0; the default where flow's 32-bit buffer
+//                   offsets do not reach, S of 2 GiB or more);
+//   panels          the same with k_chol_panel launches (BA_CHOL_FUSE=0): the
+//                   spin fallback of the other two and the test reference.
+// DESIGN.md section 15.2.  Its own translation unit, so the fused step of
+// ba_chol.hip keeps its code generation (a shared template changed the
+// inlining of the critical workgroup's factor_invert_blk; here the calls
+// force it inline).
+//   A    working matrix ((n+1) x ld), trailing part updated in place
+//   L    output factor ((n+1) x ld)
+//   Vbuf [T][64][64] inverses of the diagonal blocks
+// The panel L_{I,k} = A_{I,k} V_k^T is formed and stored once (k_chol_panel,
+// or a column task); every tile reads it from L, so a tile does one GEMM per
+// panel instead of three (the per-step form of ba_chol.hip recomputes P_I,
+// P_J per tile: 3x the flops and ~2.5x the bytes, which dominate once the
+// trailing matrix has thousands of tiles).
 #include "ba_chol.h"
 
 #include <algorithm>
@@ -20,26 +30,6 @@
 
 namespace bahip {
 
-// The rank-64 form: one block step.  k < 0: factor block 0 only (grid 1x1).
-//   A    working matrix ((n+1) x ld), trailing part updated in place
-//   L    output factor ((n+1) x ld)
-//   Vbuf [T][64][64] inverses of the diagonal blocks
-// SPLIT (large systems): the panel L_{I,k} = A_{I,k} V_k^T was formed and
-// stored by k_chol_panel just before; every tile reads it from L, so a tile
-// does one GEMM instead of three (the fused form recomputes P_I, P_J per
-// tile: 3x the flops and ~2.5x the bytes, which dominate once the trailing
-// matrix has thousands of tiles).
-// Grid: the lower tiles only, linear id -> (I, J <= I) (tile 0 = the
-// critical block); a rhs-only last tile row (n % 64 == 0) follows them.
-__device__ inline void split_tile_of(int lin, int tc, int& I, int& J) {
-  const int tri = tc * (tc + 1) / 2;
-  if (lin >= tri) { I = tc; J = lin - tri; return; }
-  int i = (int)((sqrt(8.0 * lin + 1.0) - 1.0) * 0.5);
-  while (i * (i + 1) / 2 > lin) --i;
-  while ((i + 1) * (i + 2) / 2 <= lin) ++i;
-  I = i;
-  J = lin - i * (i + 1) / 2;
-}
 // The critical workgroup of block step k: C = A_{k+1,k+1} - L_{k+1,k}
 // L_{k+1,k}^T (the panel from k_chol_panel; k < 0: block 0 as it is), then
 // factor_invert_blk; V_{k+1} and the rhs row of L leave the workgroup.
@@ -104,96 +94,7 @@ __device__ __forceinline__ void split_critical(double* __restrict__ A, double* _
   if (threadIdx.x == 0 && cw.bad) scal[SL_CHOL_BAD] += 1.0;
 }
 
-// glast (the solver's rank-64 form): the sums are grouped as the task table
-// groups them, so the factor is bitwise the scheduled forms'.  A tile's
-// products of the panels of one range [pa, pb) of the table are accumulated
-// in the MFMA accumulators, carried from step to step through U (continuing
-// an accumulation from memory rounds as continuing it in registers), and the
-// range's last panel writes A - acc; glast[(I * T + J) * T + p] marks the
-// panels that end a range of tile (I, J).  Null: every panel on its own.
-__global__ __launch_bounds__(256) void k_chol_step_split(double* __restrict__ A, double* __restrict__ L, int ld, int n,
-                                                   int k, double* __restrict__ Vbuf, double* __restrict__ scal,
-                                                   const unsigned char* __restrict__ glast,
-                                                   double* __restrict__ U) {
-  int I, J;
-  split_tile_of(blockIdx.x, (n - (k + 1) * CB + CB - 1) / CB, I, J);
-  // two tiles + a narrow inverse scratch (78 KB: two workgroups per CU, so
-  // one tile's operand loads overlap another's MFMAs); the critical
-  // workgroup forms the block inverse in S1 once C = A - P P^T consumed it
-  __shared__ double S0[CB][LDP];
-  __shared__ double S1[CB][LDP];
-  __shared__ double Zs[CB][18];
-  __shared__ CholLds cw;
-  const int nrows = n + 1;
-  const size_t lds = (size_t)ld;
-  const int s = (k + 1) * CB;                 // first row/col of the trailing matrix
-  const int kc = k * CB;                      // column offset of block k
-  const int kb = k >= 0 ? min(CB, n - kc) : 0;
-  const int r0 = s + I * CB, c0 = s + J * CB;
-  if (I == 0 && J == 0) {
-    split_critical(A, L, ld, n, k, Vbuf, scal, S0, S1, Zs, cw);
-    return;
-  }
-  // ---- trailing tile (I, J) != (0, 0)
-  if (k < 0) return;
-  if (r0 >= nrows || c0 >= n) return;
-  const TileRegs tI = tile_fetch(L, lds, r0, kc, nrows, kc + kb);   // L_{I,k}
-  TileRegs tJ;
-  if (I != J) tJ = tile_fetch(L, lds, c0, kc, n, kc + kb);          // L_{J,k}
-  // the A tile (read-modify-write target) is loaded with the operands, so
-  // its latency hides behind the staging and the MFMAs (clamped addresses,
-  // unconditional loads)
-  double av[2][2][4];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        int rr, cc;
-        acc_pos(a, b, g, &rr, &cc);
-        av[a][b][g] = A[(size_t)min(r0 + rr, nrows - 1) * ld + min(c0 + cc, n - 1)];
-      }
-  bool first = true, last = true;   // panel k starts / ends a range of this tile
-  if (glast) {
-    const int T = (n + CB - 1) / CB;
-    const unsigned char* g = glast + ((size_t)(k + 1 + I) * T + (k + 1 + J)) * T;
-    last = g[k] != 0;
-    first = k == 0 || g[k - 1] != 0;
-  }
-  d4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        int rr, cc;
-        acc_pos(a, b, g, &rr, &cc);
-        const int ri = r0 + rr, cj = c0 + cc;
-        acc[a][b][g] = (!first && ri < nrows && cj < n && cj <= ri) ? U[(size_t)ri * ld + cj] : 0.0;
-      }
-  if (I != J) tile_put(S1, tJ);
-  tile_put(S0, tI);
-  __syncthreads();
-  mfma_xyT_64_add(S0, I != J ? S1 : S0, acc);
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        int rr, cc;
-        acc_pos(a, b, g, &rr, &cc);
-        const int ri = r0 + rr, cj = c0 + cc;
-        if (ri < nrows && cj < n && cj <= ri) {
-          if (last) A[(size_t)ri * ld + cj] = av[a][b][g] - acc[a][b][g];
-          else U[(size_t)ri * ld + cj] = acc[a][b][g];
-        }
-      }
-}
-
-// Panel of block step k (SPLIT mode): L_{I,k} = A_{I,k} V_k^T for every tile
+// Panel of block step k: L_{I,k} = A_{I,k} V_k^T for every tile
 // row I > k (the rhs row included), one workgroup per tile row.
 __global__ __launch_bounds__(256) void k_chol_panel(const double* __restrict__ A, double* __restrict__ L, int ld,
                                                     int n, int k, const double* __restrict__ Vbuf) {
@@ -404,12 +305,12 @@ __device__ __forceinline__ bool upd_tile(double* __restrict__ A, double* __restr
   return ok;
 }
 
-// ---- scheduled form (default): a host-planned task table replaces the
-// per-step "every trailing tile takes panel k" update.  A task is one tile
-// and a contiguous range of panels, A_IJ -= sum_{p in [pa, pb)} L_Ip L_Jp^T,
-// so a tile is read and written once per range instead of once per panel
-// (ranges of up to `rank` panels: 4 -> a quarter of the rank-64 form's tile
-// read-modify-write traffic; the operand tiles come from L through the
+// ---- the task table: the trailing update of the whole factorisation,
+// planned on the host.  A task is one tile and a contiguous range of panels,
+// A_IJ -= sum_{p in [pa, pb)} L_Ip L_Jp^T, so a tile is read and written
+// once per range, not once per panel (ranges of up to `rank` panels,
+// kCholSplitRank = 4: a quarter of the tile read-modify-write traffic of a
+// panel-at-a-time update; the operand tiles come from L through the
 // L2 / Infinity Cache).  The chain keeps its one-step look-ahead: block step
 // k forms panel k (k_chol_panel) and then launches k_chol_upd with the
 // critical workgroup (diagonal block k + 1, panel k) and the step's tasks.
@@ -426,10 +327,11 @@ __device__ __forceinline__ bool upd_tile(double* __restrict__ A, double* __restr
 //    front-loaded trailing work becomes a steady background the chain's
 //    serial steps hide.
 // At most one task per tile per launch; bitwise deterministic for a given
-// order and rank.  The rank-64 form takes a panel per launch but groups its
-// sums by the default table's ranges (chol_rank64_groups), so it is bitwise
-// the scheduled forms too; a table of another rank (BA_CHOL_RANK != 4, 0)
-// groups differently and is not.
+// order, rank and budget: the ranges fix how every tile's sum is grouped, so
+// the three forms, which share the table, round alike.  The solver plans
+// with kCholSplitRank and budget 1 (chol_split_tasks); tools/chol_plan_check
+// checks the plan's invariants over other ranks and budgets.
+constexpr int kCholSplitRank = 4;
 struct CholSplitPlan {
   std::vector<int4> tasks;   // {I, J, pa, pb}, step-major
   std::vector<int> off;      // step k's tasks: [off[k], off[k + 1])
@@ -519,6 +421,9 @@ __global__ __launch_bounds__(256) void k_chol_upd(double* __restrict__ A, double
                                                   double* __restrict__ Vbuf, double* __restrict__ scal,
                                                   const int4* __restrict__ tasks, unsigned* vflag, unsigned epoch,
                                                   unsigned spin_max) {
+  // two tiles + a narrow inverse scratch (78 KB: two workgroups per CU, so
+  // one tile's operand loads overlap another's MFMAs); the critical
+  // workgroup forms the block inverse in S1 once C = A - P P^T consumed it
   __shared__ double S0[CB][LDP];
   __shared__ double S1[CB][LDP];
   __shared__ double Zs[CB][18];
@@ -650,35 +555,11 @@ __global__ __launch_bounds__(256, 2) void k_chol_flow(double* __restrict__ A, do
   if (threadIdx.x == 0 && !ok) atomicAdd(&scal[SL_CHOL_SPIN], 1.0);   // (the caller redoes the step per step)
 }
 
-// (the switches are read when a system is set up: ensure_dense, tools/chol_bench)
-int chol_split_rank() {
-  const char* e = getenv("BA_CHOL_RANK");
-  const int v = e ? atoi(e) : 4;
-  return v < 0 ? 4 : v;   // 0: the rank-64 form (k_chol_step_split)
-}
-static double chol_split_budget() {
-  const char* e = getenv("BA_CHOL_BUDGET");
-  const double v = e ? atof(e) : 1.0;
-  return v > 0 ? v : 1.0;
-}
-
-// The rank-64 form's summation groups: the ranges of the default task table
-// (rank 4), last[(I * T + J) * T + p] = 1 where panel p ends a range of tile
-// (I, J) (k_chol_step_split).
-void chol_rank64_groups(int n, std::vector<unsigned char>& last) {
-  const int T = (n + CB - 1) / CB, TR = (n + 1 + CB - 1) / CB;
-  CholSplitPlan P;
-  chol_split_plan(T, TR, 4, chol_split_budget(), P);
-  last.assign((size_t)TR * T * T, 0);
-  for (const int4& t : P.tasks)
-    if (t.w > t.z) last[((size_t)(t.x & 0xfffff) * T + t.y) * T + t.w - 1] = 1;
-}
-
 // The task table of an order-n system (device copy + host step offsets).
 void chol_split_tasks(int n, std::vector<int4>& tasks, std::vector<int>& off) {
   const int T = (n + CB - 1) / CB, TR = (n + 1 + CB - 1) / CB;
   CholSplitPlan P;
-  chol_split_plan(T, TR, std::max(1, chol_split_rank()), chol_split_budget(), P);
+  chol_split_plan(T, TR, kCholSplitRank, 1.0, P);
   tasks.swap(P.tasks);
   off.swap(P.off);
 }
@@ -689,19 +570,14 @@ void chol_split_tasks(int n, std::vector<int4>& tasks, std::vector<int>& off) {
 // and (k+1, k+1) — which come before every task waiting on V_{k+1} or later
 // (their due steps precede), so the in-order dispatch never fills the device
 // with tasks the chain's next V would release while one it needs is still
-// queued.  Within that, the order is a priority: a step's background tasks
-// (tiles due more than lag + 1 steps later) move behind the next `lag` steps'
-// chain-bound tasks (BA_CHOL_FLOW_LAG, default 1; 0: step order).
+// queued.  Within that, the order is a priority, by a level per task: within
+// step k, the tasks on the tiles next to the diagonal (I - J <= 2: the
+// chain's own inputs and the panel rows they are formed from) come first,
+// then the other chain-bound tasks (column tasks, and tiles due within two
+// steps); the step's background tasks move behind the next step's
+// chain-bound ones.  A task never precedes one it waits on.
 void chol_flow_tasks(const std::vector<int4>& tasks, const std::vector<int>& off, std::vector<int4>& flow) {
   const int T = (int)off.size();
-  const char* e = getenv("BA_CHOL_FLOW_LAG");
-  const int lag = e ? std::max(0, atoi(e)) : 1;
-  // the tasks on the tiles next to the diagonal (I - J <= 2: the chain's own
-  // inputs and the panel rows they are formed from) go `lead` steps ahead
-  // (BA_CHOL_FLOW_LEAD; the chain still waited ~6 us per step for them: the
-  // latency is the hand-offs themselves, not the dispatch order)
-  const char* e2 = getenv("BA_CHOL_FLOW_LEAD");
-  const int lead = e2 ? std::max(0, atoi(e2)) : 0;   // (2, 4, 8 measured slower: 2.66, 2.67, 2.73 vs 2.60 ms)
   int TR = T;
   for (const int4& t : tasks) TR = std::max(TR, (t.x & 0xfffff) + 1);
   struct E { int4 t; double level; };
@@ -714,8 +590,8 @@ void chol_flow_tasks(const std::vector<int4>& tasks, const std::vector<int>& off
       const int I = t.x & 0xfffff, J = t.y;
       const bool col = (t.x >> 20) & 1;
       const int due = I == J ? J - 2 : J - 1;
-      const bool chain = col || due <= k + lag + 1;
-      double lv = I - J <= 2 ? k - lead + 0.125 : (chain ? k + 0.25 : k + lag + 0.5);
+      const bool chain = col || due <= k + 2;
+      double lv = I - J <= 2 ? k + 0.125 : (chain ? k + 0.25 : k + 1.5);
       const int prev = last[(size_t)I * T + J];
       if (t.z > 0 && prev >= 0) lv = std::max(lv, es[prev].level + eps);
       for (int p = std::max(t.z, 1); p < t.w; ++p) {
@@ -751,22 +627,16 @@ int chol_split_fused() {
   return e && e[0] == '0' ? 0 : 1;
 }
 
-// Block step k of the split form.  tasks == null: the rank-64 form.  vflag
-// (the fused form): panel k was formed by step k - 1's column tasks (k = 0:
+// Block step k of the split form (tr tile rows below block k).  vflag (the
+// fused form): panel k was formed by step k - 1's column tasks (k = 0:
 // k_chol_panel here), else k_chol_panel forms it now.
-void launch_chol_split_step(double* A, double* L, int ld, int n, int k, int tc, int tr, double* Vbuf, double* scal,
-                            const int4* tasks, const int* off, unsigned* vflag, unsigned epoch, hipStream_t s,
-                            const unsigned char* glast, double* U) {
-  if (!vflag || !tasks || k == 0) hipLaunchKernelGGL(k_chol_panel, dim3(tr), dim3(256), 0, s, A, L, ld, n, k, Vbuf);
-  if (tasks) {
-    const char* e = getenv("BA_CHOL_SPIN_MAX");   // (diagnostics: a small bound exercises the fallback)
-    const unsigned spin = e && atoi(e) > 0 ? (unsigned)atoi(e) : (1u << 17);
-    hipLaunchKernelGGL(k_chol_upd, dim3(1 + off[k + 1] - off[k]), dim3(256), 0, s, A, L, ld, n, k, Vbuf, scal,
-                       tasks + off[k], vflag, epoch, spin);
-    return;
-  }
-  const int ntiles = tc * (tc + 1) / 2 + (tr > tc ? tc : 0);   // lower tiles (+ a rhs-only tile row)
-  hipLaunchKernelGGL(k_chol_step_split, dim3(ntiles), dim3(256), 0, s, A, L, ld, n, k, Vbuf, scal, U ? glast : nullptr, U);
+void launch_chol_split_step(double* A, double* L, int ld, int n, int k, int tr, double* Vbuf, double* scal,
+                            const int4* tasks, const int* off, unsigned* vflag, unsigned epoch, hipStream_t s) {
+  if (!vflag || k == 0) hipLaunchKernelGGL(k_chol_panel, dim3(tr), dim3(256), 0, s, A, L, ld, n, k, Vbuf);
+  const char* e = getenv("BA_CHOL_SPIN_MAX");   // (diagnostics: a small bound exercises the fallback)
+  const unsigned spin = e && atoi(e) > 0 ? (unsigned)atoi(e) : (1u << 17);
+  hipLaunchKernelGGL(k_chol_upd, dim3(1 + off[k + 1] - off[k]), dim3(256), 0, s, A, L, ld, n, k, Vbuf, scal,
+                     tasks + off[k], vflag, epoch, spin);
 }
 
 }  // namespace bahip

@@ -67,7 +67,6 @@ struct OvPlan {
   bool ok = false;                   // built, and the problem qualifies
   const int4* irec = nullptr;        // [items][4]: a pair item's 4 blocks {I, J, start, end} (zeros: none),
                                      //   or {-1 - (v G + g), 0, 0, 0} first: a diagonal slice
-  const int* item_col = nullptr;     // tile column of each item
   const unsigned* tgt = nullptr;     // [TR][T] contributions per tile and launch
   unsigned* ctr = nullptr;           // cnt [TR][T] | cam_cnt [nvc] | q [8] | pflag [TR][T]: zeroed once, cumulative
   int ioff[9] = {0};                 // queue x: items [ioff[x], ioff[x+1])
@@ -100,13 +99,12 @@ struct DevWork {
   bool wcompact;                     // W as 128-B compact records (J-free fp64 DENSE_SCHUR; ba_kernels.hip)
   double* S;                         // [(n+1) x ld] reduced system, row n = rhs (working matrix)
   double* Lf;                        // [(n+1) x ld] Cholesky factor, row n = L^-1 rhs
-  double* Ubuf;                      // [(n+1) x ld] the per-step Cholesky's update accumulator (< kCholSplitBlocks block columns, and the rank-64 form)
+  double* Ubuf;                      // [(n+1) x ld] the per-step Cholesky's update accumulator (< kCholSplitBlocks block columns; null above)
   double* Spk;                       // [n(n+1)/2 + n] packed lower triangle + rhs of S (multi-rank exchange)
   double* y;                         // [n] reduced solution
   double* Vbuf;                      // [ceil(n/64)][64][64] inverses of the diagonal Cholesky blocks
-  const int4* ctask;                 // split Cholesky task table {I, J, pa, pb} (>= kCholSplitBlocks block columns; null: rank-64 form)
+  const int4* ctask;                 // split Cholesky task table {I, J, pa, pb} (>= kCholSplitBlocks block columns; null below)
   const int* ctask_off;              // host: step k's tasks [ctask_off[k], ctask_off[k+1])
-  const unsigned char* r64_last;     // rank-64 form: [TR][T][T] panel p ends a range of the task table for tile (I, J)
   bool chol_fuse;                    // split form: column tasks form the next panel in-launch (flags: cflags[0, T))
   bool chol_flow;                    // split form: the whole factorisation as one dataflow launch (k_chol_flow)
   const int4* ftask; int nftask;     // ... its task list
@@ -236,7 +234,7 @@ void launch_reduce(const DevWork& W, uint32_t sum_mask, uint32_t max_mask, hipSt
 // the same, then (last workgroup) the scalar record to the host as launch_publish_scalars
 void launch_reduce_publish(const DevWork& W, uint32_t sum_mask, uint32_t max_mask, double* host, int n,
                            unsigned* host_seq, unsigned seq, unsigned* ticket, hipStream_t s);
-int back_flow_capacity(int device);
+int back_flow_capacity(int device);      // resident k_back_flow workgroups (-1: query failed)
 int chol_persist_capacity(int device);   // resident k_chol_persist workgroups (occupancy x CUs; -1: query failed)
 // the persistent factorisation with S formed in the same launch (W.S holds
 // nothing on entry): pairs, diagonal slices and fold of this step at radius
@@ -265,12 +263,11 @@ void launch_cov_leverage(const DevProblem& P, const DevWork& W, const int* pts, 
 bool obs_w_pc_ok(const DevProblem& P, const DevWork& W);   // k_obs_w_rc has the PCG record form for this source
 bool chol_persist_fits(int device, int n);   // every workgroup of k_chol_persist resident at once
 void chol_split_tasks(int n, std::vector<int4>& tasks, std::vector<int>& off);   // the split form's task table
-int chol_split_rank();
-void chol_rank64_groups(int n, std::vector<unsigned char>& last);   // the rank-64 form's summation groups (the task table's ranges)
 int chol_split_fused();                      // BA_CHOL_FUSE (default 1)
 int chol_split_flow();                       // BA_CHOL_FLOW (default 1)
-void chol_flow_tasks(const std::vector<int4>& tasks, const std::vector<int>& off, std::vector<int4>& flow);                       // panels per split-Cholesky task (BA_CHOL_RANK, default 4; 0: rank-64 form)
-int chol_split_blocks();                     // block columns from which the split step form is used   // resident k_back_flow workgroups (-1: query failed)
+// the task table as the flow form's one list, in dispatch order
+void chol_flow_tasks(const std::vector<int4>& tasks, const std::vector<int>& off, std::vector<int4>& flow);
+int chol_split_blocks();                     // block columns from which the split step form is used
 constexpr int kLinLdsCamsHost = 200;   // = kLinLdsCams (ba_kernels.hip): cameras the LDS camera table holds
 constexpr int kWcCamsHost = 1024;      // variable cameras of the compact-W DENSE_SCHUR pair pass
 int jr_ja_host(int nc);   // JA stride of the JR records for nc cameras (12 or 14)

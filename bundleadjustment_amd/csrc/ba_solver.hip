@@ -578,11 +578,8 @@ void build_overlap_plan(ba_ctx* ctx, const std::vector<int4>& blocks) {
   for (int I = 0; I < TR; ++I)
     for (int J = 0; J < T && J <= I; ++J)
       if (tgt[(size_t)I * T + J] == 0) return;   // (a lower tile nothing writes)
-  std::vector<int4> items[8];
-  std::vector<int> icol[8];
+  std::vector<int4> items[8];   // four records to an item
   int unit_rr = 0;
-  const char* fe = std::getenv("BA_OV_FIRST_COLS");
-  const int first_cols = fe ? std::max(0, atoi(fe)) : 0;
   for (int tc = 0; tc < T; ++tc) {
     for (int v = 0; v < nvc; ++v) {
       if ((6 * v) >> 6 != tc) continue;
@@ -590,7 +587,6 @@ void build_overlap_plan(ba_ctx* ctx, const std::vector<int4>& blocks) {
         const int x = unit_rr++ & 7;
         items[x].push_back(make_int4(-1 - (v * G + g), 0, 0, 0));
         for (int q = 1; q < 4; ++q) items[x].push_back(make_int4(0, 0, 0, 0));
-        icol[x].push_back(tc);
       }
     }
     const std::vector<int>& cb = colblk[tc];
@@ -605,29 +601,22 @@ void build_overlap_plan(ba_ctx* ctx, const std::vector<int4>& blocks) {
         acc += blocks[cb[k]].w - blocks[cb[k]].z;
         run.push_back(cb[k++]);
       }
-      // (BA_OV_FIRST_COLS, default 0: the first columns one block to an item,
-      // meant to start the chain sooner — measured slower, C3 0.64 ms with
-      // column 0 alone, 0.97 with every column, vs 0.58: an item's fixed cost
-      // outweighs its length; profiles/r06_v11_ov_first_cols_ab.txt)
-      const int per = tc < first_cols ? 1 : 4;
-      for (size_t r = 0; r < run.size(); r += per) {
-        for (int q = 0; q < 4; ++q)
-          items[x].push_back(q < per && r + q < run.size() ? blocks[run[r + q]] : make_int4(0, 0, 0, 0));
-        icol[x].push_back(tc);
-      }
+      // four pair blocks to an item.  (Measured and not kept: one block to an
+      // item in the first columns, to start the chain sooner — C3 0.64 to
+      // 0.97 ms vs 0.58: an item's fixed cost outweighs its length;
+      // profiles/r06_v11_ov_first_cols_ab.txt.)
+      for (size_t r = 0; r < run.size(); r += 4)
+        for (int q = 0; q < 4; ++q) items[x].push_back(r + q < run.size() ? blocks[run[r + q]] : make_int4(0, 0, 0, 0));
     }
   }
   std::vector<int4> all;
-  std::vector<int> allc;
   OvPlan& P = W.ov;
   for (int x = 0; x < 8; ++x) {
-    P.ioff[x] = (int)allc.size();
+    P.ioff[x] = (int)(all.size() / 4);
     all.insert(all.end(), items[x].begin(), items[x].end());
-    allc.insert(allc.end(), icol[x].begin(), icol[x].end());
   }
-  P.ioff[8] = (int)allc.size();
+  P.ioff[8] = (int)(all.size() / 4);
   P.irec = ctx->upload(all);
-  P.item_col = ctx->upload(allc);
   P.tgt = ctx->upload(tgt);
   const size_t nctr = 2 * (size_t)TR * T + nvc + 8;   // cnt | cam_cnt | q | pflag
   P.ctr = ctx->dalloc<unsigned>(nctr);
@@ -694,20 +683,13 @@ void ensure_dense(ba_ctx* ctx) {
   DevWork& W = ctx->W;
   W.S = ctx->dalloc<double>((size_t)(ctx->n + 1) * std::max(ctx->ld, 1));
   W.Lf = ctx->dalloc<double>((size_t)(ctx->n + 1) * std::max(ctx->ld, 1));
-  const bool rank64 = (ctx->n + 63) / 64 >= bahip::chol_split_blocks() && bahip::chol_split_rank() == 0;
-  W.Ubuf = (ctx->n + 63) / 64 < bahip::chol_split_blocks() || rank64
-               ? ctx->dalloc<double>((size_t)(ctx->n + 1) * std::max(ctx->ld, 1)) : nullptr;
-  W.r64_last = nullptr;
-  if (rank64) {
-    std::vector<unsigned char> last;
-    bahip::chol_rank64_groups(ctx->n, last);
-    W.r64_last = ctx->upload(last);
-  }
+  const bool split = (ctx->n + 63) / 64 >= bahip::chol_split_blocks();
+  W.Ubuf = split ? nullptr : ctx->dalloc<double>((size_t)(ctx->n + 1) * std::max(ctx->ld, 1));
   W.Vbuf = ctx->dalloc<double>((size_t)((ctx->n + 63) / 64 + 1) * 64 * 64);
   W.ctask = nullptr;
   W.ctask_off = nullptr;
   std::vector<int4> tasks_h;
-  if ((ctx->n + 63) / 64 >= bahip::chol_split_blocks() && bahip::chol_split_rank() > 0) {
+  if (split) {
     bahip::chol_split_tasks(ctx->n, tasks_h, ctx->chol_off);
     W.ctask = ctx->upload(tasks_h);
     W.ctask_off = ctx->chol_off.data();

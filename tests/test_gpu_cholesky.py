@@ -23,7 +23,6 @@ its figures, `pytest -s`):
   flow          0.0032        6.0e-16 (n=1542) 0.0099        3.6e-15
   fused         0.0032        6.0e-16          0.0099        3.6e-15
   panels        0.0032        6.0e-16          0.0099        3.6e-15
-  rank64        0.0032        6.0e-16          0.0099        3.6e-15
 (solve_error bounds: 6.5e-12 at n = 1470, 6.9e-8 at n = 1542 with kappa =
 1e10.)  The forms of one family give identical figures: they are bitwise
 equal (test_forms_agree_bitwise_on_injected_systems).
@@ -42,7 +41,7 @@ pytestmark = pytest.mark.gpu
 
 CB = 64
 SPLIT_BLOCKS = 24   # kCholSplitBlocks (ba_chol.hip)
-KNOBS = ("BA_CHOL_PERSIST", "BA_CHOL_FLOW", "BA_CHOL_FUSE", "BA_CHOL_RANK", "BA_CHOL_SPIN_MAX", "BA_CHOL_OVERLAP")
+KNOBS = ("BA_CHOL_PERSIST", "BA_CHOL_FLOW", "BA_CHOL_FUSE", "BA_CHOL_SPIN_MAX", "BA_CHOL_OVERLAP")
 
 # variable cameras -> order n = 6 nvc; T = ceil(n / 64) block columns, b = the last block's width
 NVC = (1, 2, 3, 5, 8, 10,   # one partial tile: 6, 12, 18 (crosses sub-panel 0), 30, 48 (b % 16 == 0, m = 49), 60
@@ -51,8 +50,7 @@ NVC = (1, 2, 3, 5, 8, 10,   # one partial tile: 6, 12, 18 (crosses sub-panel 0),
        245, 246, 256, 257)  # T = 23 (largest persistent), 24 (first split, b = 4), 24 with n % 64 == 0, 25 (b = 6)
 
 FORMS_SMALL = {"persistent": {}, "per_step": {"BA_CHOL_PERSIST": "0"}}
-FORMS_SPLIT = {"flow": {}, "fused": {"BA_CHOL_FLOW": "0"}, "panels": {"BA_CHOL_FLOW": "0", "BA_CHOL_FUSE": "0"},
-               "rank64": {"BA_CHOL_RANK": "0"}}
+FORMS_SPLIT = {"flow": {}, "fused": {"BA_CHOL_FLOW": "0"}, "panels": {"BA_CHOL_FLOW": "0", "BA_CHOL_FUSE": "0"}}
 
 
 def forms_of(n):
@@ -156,16 +154,8 @@ def test_forms_agree_bitwise_on_injected_systems(monkeypatch, n, ref_form, form)
     """The forms run the same arithmetic in the same order per tile: on an
     injected dense system (not the scene-shaped matrices of the trajectory
     tests) the stored L rows, the lower triangles of V and y are bitwise
-    equal: per-step against persistent at n = 192, fused / panels / rank-64
-    against flow at n = 1536.
-
-    This test found the rank-64 form (BA_CHOL_RANK=0, k_chol_step_split) not
-    bitwise the scheduled forms: 850119 entries of L, 41280 of V's lower
-    triangles and 1511 of y differed at n = 1536, by at most 8.3e-15 (L) and
-    4.4e-15 (y).  It subtracted every panel's product from a tile on its own,
-    A = (A - u_0) - u_1 ..., where the task table's forms sum a range of up to
-    four panels in the MFMA accumulators first, A - (u_0 + .. + u_3).  It now
-    groups its sums by the default table's ranges (chol_rank64_groups)."""
+    equal: per-step against persistent at n = 192, fused / panels against
+    flow at n = 1536."""
     sysm = [cr.system(n, 1e2, n)]
     a, = factor(monkeypatch, n, ref_form, sysm)
     b, = factor(monkeypatch, n, form, sysm)

@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # A/B: the default C3 bench under alternative environment settings, interleaved.
-#   tools/ab_env.sh "BA_CAM_PT=0" "BA_CAM_PT=1"
+#   tools/ab_env.sh "BA_CHOL_OVERLAP=1" "BA_CHOL_OVERLAP=0"
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 for round in 1 2; do
