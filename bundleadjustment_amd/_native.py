@@ -17,6 +17,9 @@ BA_ABI_VERSION = 2          # include/ba_hip.h
 STATUS_NAMES = {0: "BA_OK", 1: "BA_ERR_INVALID_ARGUMENT", 2: "BA_ERR_DEVICE", 3: "BA_ERR_OUT_OF_MEMORY",
                 4: "BA_ERR_NO_PROBLEM", 5: "BA_ERR_COMM", 6: "BA_ERR_SINGULAR"}
 TERMINATION_NAMES = {0: "CONVERGENCE", 1: "NO_CONVERGENCE", 2: "FAILURE"}
+# ba_debug_plan's int32 values, in the header's order (BA_DEBUG_PLAN_FIELDS of them)
+DEBUG_PLAN_FIELDS = ["nvc", "nblocks", "neblocks", "s_memset", "dup_diag", "chol_persist", "ov_ok", "wcompact",
+                     "jdiag", "jrfree", "have_dense", "have_pcg", "npchunks", "pcg_ndup", "pcgc", "pacc", "pcgjf"]
 
 
 class NativeLibraryError(RuntimeError):
@@ -230,6 +233,7 @@ SIGNATURES = [
                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     ("ba_debug_factor", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_int)]),
+    ("ba_debug_plan", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     ("ba_prune", C.c_int, [C.c_void_p, C.POINTER(ba_prune_problem), C.c_void_p]),
     ("ba_solve_pose_batch", C.c_int, [C.c_void_p, C.POINTER(ba_pose_batch), C.POINTER(ba_options), C.c_void_p,
                                       C.POINTER(ba_summary)]),

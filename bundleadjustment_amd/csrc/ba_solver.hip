@@ -2918,6 +2918,19 @@ int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double*
   });
 }
 
+int ba_debug_plan(ba_ctx* ctx, int32_t* out, int n) {
+  if (!ctx || !out || n < 0) return BA_ERR_INVALID_ARGUMENT;
+  if (!ctx->have_problem) return BA_ERR_NO_PROBLEM;
+  // host state only (the order of include/ba_hip.h): nothing is built or launched
+  const DevWork& W = ctx->W;
+  const int32_t v[BA_DEBUG_PLAN_FIELDS] = {
+      ctx->nvc, W.nblocks, W.neblocks, W.s_memset, ctx->have_dense && ctx->dup_diag, W.chol_persist, W.ov.ok,
+      W.wcompact, W.jdiag, W.jrfree, ctx->have_dense, ctx->have_pcg, W.npchunks,
+      ctx->have_pcg ? (int32_t)std::min<size_t>(ctx->pcg_ndup, INT32_MAX) : 0, W.pcgc, W.pacc, W.pcgjf};
+  std::copy(v, v + std::min(n, (int)BA_DEBUG_PLAN_FIELDS), out);
+  return BA_OK;
+}
+
 int ba_debug_factor(ba_ctx* ctx, const double* S_in, const double* rhs_in, double* L, double* V, double* y, int* ok) {
   if (!ctx) return BA_ERR_INVALID_ARGUMENT;
   return guarded(ctx, [&] { debug_factor(ctx, S_in, rhs_in, L, V, y, ok); });

@@ -260,6 +260,14 @@ class Solver:
                                              C.byref(n)), "ba_debug_blocks")
         return {"Hpp": Hpp, "gp": gp, "Hcc": Hcc, "gc": gc, "S": S, "rhs": rhs, "n": n.value}
 
+    def debug_plan(self) -> dict:
+        """The dispatch decisions the host made for the current problem as of
+        the last solve / debug_blocks (ba_debug_plan: host state only, nothing
+        built or launched): N.DEBUG_PLAN_FIELDS as a dict of ints."""
+        out = (C.c_int32 * len(N.DEBUG_PLAN_FIELDS))()
+        self._check(self.lib.ba_debug_plan(self.h, out, len(out)), "ba_debug_plan")
+        return dict(zip(N.DEBUG_PLAN_FIELDS, (int(v) for v in out)))
+
     def reduced_order(self) -> int:
         """Order n of the current problem's reduced camera system: 6 x the
         variable cameras that have an observation."""

@@ -807,6 +807,36 @@ int ba_two_view_hypotheses_e5(ba_ctx* ctx, const ba_two_view_batch* batch, const
 int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double* Hcc, double* gc, double* S,
                     double* rhs, int* n_out);
 
+/* Test / inspection: the dispatch decisions the host has made for the current
+ * problem, as of the last ba_solve / ba_debug_blocks (a read-only copy of host
+ * state: nothing is built and nothing is launched; before the first solve the
+ * structures are not built and their fields are 0).  Writes the first
+ * min(n, BA_DEBUG_PLAN_FIELDS) of these int32 values to out, in this order:
+ *    0 nvc           observed variable cameras (the reduced system has 6 nvc rows)
+ *    1 nblocks       DENSE_SCHUR pair blocks (co-observed camera pairs, (I, I) included)
+ *    2 neblocks      lower blocks of S no pair writes, zeroed from a list each step
+ *    3 s_memset      ... or the whole of S is cleared by a memset each step
+ *    4 dup_diag      a pair block (I, I) exists (a point seen twice by one camera)
+ *    5 chol_persist  the factorisation runs as one persistent launch
+ *    6 ov_ok         the overlapped form's plan was built (S formed in that launch)
+ *    7 wcompact      W as compact 128-byte records
+ *    8 jdiag         the diagonal Schur blocks formed without stored J
+ *    9 jrfree        the iteration never stores J (0: BA_JR=1)
+ *   10 have_dense    the DENSE_SCHUR structures are built
+ *   11 have_pcg      the ITERATIVE_SCHUR structures are built
+ *   12 npchunks      point-aligned chunks of the PCG point pass (0: a point has
+ *                    more than 64 observations, or BA_PCG_SEG=0)
+ *   13 pcg_ndup      ITERATIVE_SCHUR duplicate (camera, point) observation pairs
+ *   14 pcgc          the PCG point pass reads the 16-value records
+ *   15 pacc          the back substitution uses the CG's accumulated point products
+ *   16 pcgjf         the PCG point pass forms its records itself (no W)
+ * Fields 7-9 and 14-16 are decided per step from the options and the
+ * environment: they describe the last step enqueued.
+ * Errors: BA_ERR_INVALID_ARGUMENT for a NULL ctx or out or n < 0 (no device
+ * needed); BA_ERR_NO_PROBLEM before ba_set_problem. */
+#define BA_DEBUG_PLAN_FIELDS 17
+int ba_debug_plan(ba_ctx* ctx, int32_t* out, int n);
+
 /* Test / inspection: run the DENSE_SCHUR factorisation + back substitution a
  * solve's step runs (the context's own dispatch: whatever form the order and
  * the BA_CHOL_* knobs select) on a caller-supplied system of the current
