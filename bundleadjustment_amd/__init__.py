@@ -6,10 +6,11 @@ of include/ba_hip.h (libba_hip.so).  This package is the thin host side:
 ctypes binding, problem container, synthetic problem generator, and the
 optimizer classes that mirror the reference's API (Optimizer.h:196-289).
 """
-from .problem import (Problem, TriangulationBatch, WindowBatch, make_config, make_synthetic,  # noqa: F401
-                      pack_window_batch, shard_points, triangulation_batch, HUBER_A)
+from .problem import (MatchBatch, Problem, TriangulationBatch, WindowBatch, make_config, make_synthetic,  # noqa: F401
+                      pack_match_batch, pack_window_batch, shard_points, triangulation_batch, HUBER_A)
 from ._native import BAError  # noqa: F401
 from .solver import Options, Solver, Summary, solve  # noqa: F401
 
-__all__ = ["Problem", "TriangulationBatch", "WindowBatch", "make_config", "make_synthetic", "pack_window_batch",
+__all__ = ["MatchBatch", "Problem", "TriangulationBatch", "WindowBatch", "make_config", "make_synthetic", "pack_match_batch",
+           "pack_window_batch",
            "shard_points", "triangulation_batch", "HUBER_A", "Options", "Solver", "Summary", "solve", "BAError"]

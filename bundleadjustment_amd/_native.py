@@ -177,6 +177,29 @@ TV_AUTO, TV_ESSENTIAL, TV_HOMOGRAPHY = range(3)
 TV_E_EIGHT_POINT, TV_E_FIVE_POINT = range(2)     # ba_two_view_options.reserved
 
 
+class ba_match_batch(C.Structure):
+    _fields_ = [
+        ("dim", C.c_int32), ("n_sets", C.c_int32), ("n_pairs", C.c_int32), ("n_ref", C.c_int32),
+        ("set_offset", C.c_void_p), ("desc", C.c_void_p), ("pair_query", C.c_void_p), ("pair_train", C.c_void_p),
+        ("row_ref", C.c_void_p), ("ref_desc", C.c_void_p),
+    ]
+
+
+class ba_match_options(C.Structure):
+    _fields_ = [("ratio", C.c_float), ("unique", C.c_int32), ("max_distance", C.c_float), ("reserved", C.c_int32)]
+
+
+class ba_match(C.Structure):
+    _fields_ = [
+        ("query", C.c_int32), ("train", C.c_int32), ("distance", C.c_float), ("second_distance", C.c_float),
+        ("ref_distance", C.c_float),
+    ]
+
+
+class ba_match_neighbors(C.Structure):
+    _fields_ = [("idx0", C.c_int32), ("idx1", C.c_int32), ("d2_0", C.c_float), ("d2_1", C.c_float)]
+
+
 class ba_covariance_request(C.Structure):
     _fields_ = [
         ("n_cam_pairs", C.c_int32), ("n_points", C.c_int32), ("cam_pairs", C.c_void_p), ("cam_cov", C.c_void_p),
@@ -258,6 +281,11 @@ SIGNATURES = [
     ("ba_two_view_hypotheses", C.c_int, [C.c_void_p, C.POINTER(ba_two_view_batch), C.POINTER(ba_two_view_options),
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    ("ba_match_defaults", None, [C.POINTER(ba_match_options)]),
+    ("ba_match_descriptors", C.c_int, [C.c_void_p, C.POINTER(ba_match_batch), C.POINTER(ba_match_options), C.c_void_p,
+                                       C.c_void_p]),
+    ("ba_match_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ba_match_knn", C.c_int, [C.c_void_p, C.POINTER(ba_match_batch), C.c_int, C.c_void_p]),
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
     ("ba_covariance_ex", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request_ex)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

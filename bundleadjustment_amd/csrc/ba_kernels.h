@@ -426,6 +426,34 @@ void launch_two_view(const TvArgs& A, hipStream_t s);
 void launch_two_view_hypotheses(const TvArgs& A, const TvDebug& D, hipStream_t s);
 void launch_two_view_hypotheses_e5(const TvArgs& A, const TvDebug& D, hipStream_t s);
 
+// batched descriptor matching: exact 2-NN, ratio test, unique-train filter (ba_match.hip)
+struct MatchArgs {
+  int n_pair, dim;
+  int rows, n_ref;                 // descriptor rows of all sets; reference descriptors (0 without row_ref)
+  int max_nq, max_nt;              // largest query / train set of the pairs
+  int chunks, chunk_rows;          // MatchPlan: train chunks per query tile, rows per chunk
+  int select;                      // 0: ba_match_knn (the dense records only)
+  int unique;
+  float ratio, max_distance;
+  // inputs
+  const MatchPair* pair;           // [n_pair]
+  const float* desc;               // [rows][dim]
+  const int* row_ref;              // [rows] or null
+  const float* ref;                // [n_ref][dim]
+  // scratch
+  float* norms;                    // [rows + n_ref]: nrm of every descriptor, then of every reference
+  unsigned long long* part;        // [NQ][chunks][2]: partial top-2 keys
+  uint8_t* surv;                   // [NQ]: the query passed the ratio test
+  unsigned long long* win;         // [NT]: unique: the winning (bits(d2) << 32 | query) per train row (all ones: none)
+  int* hist;                       // [NT]: !unique: survivors per train row, then their first slot
+  // outputs
+  ba_match_neighbors* knn;         // [NQ]
+  int* cnt;                        // [n_pair]
+  ba_match* matches;               // [NM] at MatchPair::moff
+};
+// ev: three events recorded after the norms, the 2-NN and the selection (null: none)
+void launch_match(const MatchArgs& A, hipStream_t s, hipEvent_t* ev);
+
 int grid_for(int n);
 int pt_group_grid(int np);   // grid of the kPtLanes-lanes-per-point kernels
 

@@ -110,9 +110,9 @@ struct ba_ctx {
   unsigned* d_ticket = nullptr;  // k_reduce<true>'s last-workgroup ticket (zero between launches)
   unsigned scal_seq = 0;
   // staging of ba_solve_pose_batch, ba_solve_window_batch, ba_triangulate,
-  // ba_pnp_ransac and ba_two_view_ransac (one each: a call of one never makes
-  // another reallocate)
-  StagingArena pose, win, tri, pnp, tv;
+  // ba_pnp_ransac, ba_two_view_ransac and ba_match_descriptors (one each: a
+  // call of one never makes another reallocate)
+  StagingArena pose, win, tri, pnp, tv, match;
   // ba_solve_window_batch: the last call's logs and times
   std::vector<ba_iteration> win_log;   // [n_problems][win_log_cap]
   std::vector<int> win_log_n;
@@ -121,6 +121,8 @@ struct ba_ctx {
   std::vector<double> tri_ms;          // ba_triangulate_times of the last call
   std::vector<double> pnp_ms;          // ba_pnp_times of the last call
   std::vector<double> tv_ms;           // ba_two_view_times of the last call
+  std::vector<double> match_ms;        // ba_match_times of the last call
+  hipEvent_t match_ev[3] = {nullptr, nullptr, nullptr};   // phase stamps of ba_match_descriptors (created by its first call)
 
   // host copies of the sorted structure, kept for the lazily built
   // linear-solver structures (Schur pair lists / PCG duplicate pairs)
@@ -2079,7 +2081,8 @@ int ba_destroy(ba_ctx* ctx) {
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
-  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv}) (void)hipFree(a->dev);
+  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv, &ctx->match}) (void)hipFree(a->dev);
+  for (hipEvent_t e : ctx->match_ev) if (e) (void)hipEventDestroy(e);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -2858,6 +2861,134 @@ int ba_two_view_hypotheses_e5(ba_ctx* ctx, const ba_two_view_batch* b, const ba_
     for (int i = 0; i < n; ++i)
       for (int sidx = 0; sidx < 10; ++sidx)
         std::memcpy(E + 9 * (10 * (size_t)i + sidx), m + 9 * ((size_t)sidx * n + i), sizeof(double) * 9);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// ba_match_descriptors: host side.  Validation, the pair table and the section
+// layout are plain C++ (check_match, match_plan, match_layout:
+// host/ba_batch_pack.hpp); the tables go up through the staging copy and the
+// descriptors from the caller's array, then the launches of ba_match.hip and
+// one download.  The context's current problem is not touched.
+// ---------------------------------------------------------------------------
+void ba_match_defaults(ba_match_options* opt) {
+  if (opt) match_defaults(*opt);
+}
+
+namespace {
+
+// the batch (pairs [first, first + n) of it) into the arena's host copy and
+// onto the device; the kernel arguments
+MatchArgs match_stage(ba_ctx* ctx, const ba_match_batch* b, const ba_match_options& p, const MatchPlan& M,
+                      const MatchLayout& P, bool knn, const std::string& fn) {
+  const size_t rows = b->n_sets > 0 ? (size_t)b->set_offset[b->n_sets] : 0, dim = (size_t)b->dim;
+  const bool have_ref = b->row_ref != nullptr;
+  const size_t n_ref = have_ref ? (size_t)b->n_ref : 0;
+  HIP_OK(hipSetDevice(ctx->device));
+  ctx->match.reserve(ctx, P.L.total, fn);
+  // The descriptors are the bulk of the batch (125 MB for 256 pairs of 1000 x 1000) and the last input
+  // section: they go up from the caller's array, which the call outlives, not through the host copy.
+  std::vector<char>& h = ctx->match.host;
+  h.resize(P.L.io_b);
+  std::memset(h.data(), 0, P.desc);
+  stage(h, P.pair, M.pair.data(), sizeof(MatchPair) * M.pair.size());
+  if (have_ref) {
+    stage(h, P.row_ref, b->row_ref, sizeof(int32_t) * rows);
+    if (b->ref_desc) stage(h, P.ref, b->ref_desc, sizeof(float) * n_ref * dim);
+  }
+  char* d = ctx->match.dev;
+  if (P.desc) HIP_OK(hipMemcpyAsync(d, h.data(), P.desc, hipMemcpyHostToDevice, ctx->stream));
+  if (rows) HIP_OK(hipMemcpyAsync(d + P.desc, b->desc, sizeof(float) * rows * dim, hipMemcpyHostToDevice, ctx->stream));
+  MatchArgs A{};
+  A.n_pair = (int)M.pair.size(); A.dim = b->dim; A.rows = (int)rows; A.n_ref = (int)n_ref;
+  A.max_nq = M.max_nq; A.max_nt = M.max_nt; A.chunks = M.chunks; A.chunk_rows = M.chunk_rows;
+  A.select = knn ? 0 : 1; A.unique = p.unique; A.ratio = p.ratio; A.max_distance = p.max_distance;
+  A.pair = at<const MatchPair>(d, P.pair); A.desc = at<const float>(d, P.desc);
+  A.row_ref = have_ref ? at<const int>(d, P.row_ref) : nullptr; A.ref = at<const float>(d, P.ref);
+  A.norms = at<float>(d, P.norms); A.part = at<unsigned long long>(d, P.part); A.knn = at<ba_match_neighbors>(d, P.knn);
+  if (!knn) {
+    A.surv = at<uint8_t>(d, P.surv); A.win = at<unsigned long long>(d, P.win); A.hist = at<int>(d, P.hist);
+    A.cnt = at<int>(d, P.cnt); A.matches = at<ba_match>(d, P.matches);
+    if (M.NT) {   // no winner, no survivor yet
+      HIP_OK(hipMemsetAsync(A.win, 0xff, sizeof(uint64_t) * M.NT, ctx->stream));
+      HIP_OK(hipMemsetAsync(A.hist, 0, sizeof(int32_t) * M.NT, ctx->stream));
+    }
+  }
+  return A;
+}
+
+}  // namespace
+
+int ba_match_descriptors(ba_ctx* ctx, const ba_match_batch* b, const ba_match_options* opt, int32_t* match_offset,
+                         ba_match* matches) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_match_descriptors: ";
+    const ba_match_options p = check_match(fn.c_str(), b, opt);
+    if (!match_offset) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const size_t N = b->n_pairs;
+    match_offset[0] = 0;
+    if (N == 0) return;
+    const double t0 = now_s();
+    const MatchPlan M = match_plan(fn.c_str(), b, p.unique, 0, (int)N);
+    if (M.NM > 0 && !matches) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const size_t rows = (size_t)b->set_offset[b->n_sets];
+    const MatchLayout P = match_layout(M, rows, (size_t)b->n_ref, b->dim, b->row_ref != nullptr, false);
+    HIP_OK(hipSetDevice(ctx->device));
+    for (hipEvent_t& e : ctx->match_ev)
+      if (!e) HIP_OK(hipEventCreate(&e));
+    const MatchArgs A = match_stage(ctx, b, p, M, P, false, fn);
+    const double t_prep = now_s() - t0;
+    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
+    launch_match(A, ctx->stream, ctx->match_ev);
+    HIP_OK(hipGetLastError());
+    std::vector<char>& h = ctx->match.host;
+    char* d = ctx->match.dev;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    float ms[3] = {0.0f, 0.0f, 0.0f};
+    HIP_OK(hipEventElapsedTime(&ms[0], ctx->ev[0], ctx->match_ev[0]));
+    HIP_OK(hipEventElapsedTime(&ms[1], ctx->match_ev[0], ctx->match_ev[1]));
+    HIP_OK(hipEventElapsedTime(&ms[2], ctx->match_ev[1], ctx->match_ev[2]));
+    const int* cnt = at<const int>(h.data(), P.cnt);
+    const ba_match* rec = at<const ba_match>(h.data(), P.matches);
+    size_t o = 0;
+    for (size_t i = 0; i < N; ++i) {
+      const MatchPair& Q = M.pair[i];
+      const int c = std::min(std::max(cnt[i], 0), Q.cap);
+      if (c) std::memcpy(matches + o, rec + Q.moff, sizeof(ba_match) * (size_t)c);
+      o += (size_t)c;
+      match_offset[i + 1] = (int32_t)o;
+    }
+    ctx->match_ms = {1e3 * t_prep, (double)(ms[0] + ms[1] + ms[2]), 1e3 * (now_s() - t0), (double)ms[0], (double)ms[1],
+                     (double)ms[2]};
+  });
+}
+
+int ba_match_times(ba_ctx* ctx, double* ms, int n) {
+  return ctx ? copy_times(ctx->match_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
+}
+
+int ba_match_knn(ba_ctx* ctx, const ba_match_batch* b, int pair, ba_match_neighbors* out) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_match_knn: ";
+    const ba_match_options p = check_match(fn.c_str(), b, nullptr);
+    if (pair < 0 || pair >= b->n_pairs)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " out of range"};
+    const MatchPlan M = match_plan(fn.c_str(), b, 1, pair, 1);
+    if (M.NQ == 0) return;
+    if (!out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const size_t rows = (size_t)b->set_offset[b->n_sets];
+    const MatchLayout P = match_layout(M, rows, (size_t)b->n_ref, b->dim, b->row_ref != nullptr, true);
+    const MatchArgs A = match_stage(ctx, b, p, M, P, true, fn);
+    launch_match(A, ctx->stream, nullptr);
+    HIP_OK(hipGetLastError());
+    std::vector<char>& h = ctx->match.host;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, ctx->match.dev + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost,
+                          ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(out, h.data() + P.knn, sizeof(ba_match_neighbors) * M.NQ);
   });
 }
 

@@ -1,7 +1,7 @@
 // ba_batch_pack.hpp — host-only packing shared by the batch entry points of
 // ba_solver.hip: the error type, the section layout of a staging buffer, the
 // CSR-offset validation, the summary record, the validation and layout of
-// ba_pnp_ransac and ba_two_view_ransac, and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
+// ba_pnp_ransac, ba_two_view_ransac and ba_match_descriptors, and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
 // plain C++17 without a HIP header and runs under ASan + UBSan
 // (tests/cpp/batch_pack.cpp, `make -C tests/cpp sanitize`).
 #pragma once
@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <string>
 #include <utility>
 #include <vector>
@@ -212,6 +213,132 @@ inline void two_view_pack_matches(const ba_two_view_batch* b, size_t NM, float* 
     dst[4 * k] = b->uv1[2 * k]; dst[4 * k + 1] = b->uv1[2 * k + 1];
     dst[4 * k + 2] = b->uv2[2 * k]; dst[4 * k + 3] = b->uv2[2 * k + 1];
   }
+}
+
+// ---------------------------------------------------------------------------
+// ba_match_descriptors / ba_match_knn
+// ---------------------------------------------------------------------------
+inline void match_defaults(ba_match_options& o) {
+  o.ratio = 0.7f; o.unique = 1; o.max_distance = std::numeric_limits<float>::infinity(); o.reserved = 0;
+}
+
+constexpr int kMatchQTile = 128;        // query rows per workgroup of the 2-NN kernel
+constexpr int kMatchTTile = 64;         // train rows per staged tile
+constexpr int kMatchMaxRows = 65535 * kMatchQTile;   // a grid dimension holds a set's query tiles
+
+// One pair as the kernels read it
+struct MatchPair {
+  int q0, nq;      // the query set: first row in desc, rows
+  int t0, nt;      // the train set
+  int qoff;        // first dense 2-NN record (sum of nq of the pairs before)
+  int toff;        // first per-train slot (sum of nt of the pairs before)
+  int moff;        // first match record (sum of the capacities of the pairs before)
+  int cap;         // match capacity: min(nq, nt) with unique, else nq
+};
+
+// Everything the kernels index with or branch on, checked on the host; the
+// options are returned with the defaults applied.
+inline ba_match_options check_match(const char* fn, const ba_match_batch* b, const ba_match_options* opt) {
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what}; };
+  if (!b || b->n_sets < 0 || b->n_pairs < 0 || b->n_ref < 0) throw invalid("bad batch");
+  if (b->dim != 64 && b->dim != 128) throw invalid("dim " + std::to_string(b->dim) + " is neither 64 nor 128");
+  ba_match_options p;
+  if (opt) p = *opt; else match_defaults(p);
+  if (!(p.ratio >= 0.0f && p.ratio <= std::numeric_limits<float>::max())) throw invalid("ratio must be non-negative and finite");
+  if (!(p.max_distance >= 0.0f)) throw invalid("max_distance must be non-negative");
+  if (p.unique != 0 && p.unique != 1) throw invalid("unknown unique " + std::to_string(p.unique));
+  if (p.reserved != 0) throw invalid("reserved must be 0");
+  if (b->n_sets > 0 && !b->set_offset) throw invalid("null array");
+  if (b->n_sets > 0) check_offsets(fn, "set_offset", b->set_offset, b->n_sets, "set");
+  const int rows = b->n_sets > 0 ? b->set_offset[b->n_sets] : 0;
+  for (int s = 0; s < b->n_sets; ++s)
+    if (b->set_offset[s + 1] - b->set_offset[s] > kMatchMaxRows)
+      throw invalid("set " + std::to_string(s) + " has more than " + std::to_string(kMatchMaxRows) + " rows");
+  if (rows > 0 && !b->desc) throw invalid("null array");
+  if (b->n_pairs > 0 && (!b->pair_query || !b->pair_train)) throw invalid("null array");
+  for (int i = 0; i < b->n_pairs; ++i)
+    if (b->pair_query[i] < 0 || b->pair_query[i] >= b->n_sets || b->pair_train[i] < 0 || b->pair_train[i] >= b->n_sets)
+      throw invalid("pair " + std::to_string(i) + " names a set out of range");
+  if (b->row_ref)
+    for (int r = 0; r < rows; ++r) {
+      if (b->row_ref[r] < -1 || b->row_ref[r] >= b->n_ref)
+        throw invalid("row_ref[" + std::to_string(r) + "] out of range");
+      if (b->row_ref[r] >= 0 && !b->ref_desc) throw invalid("row_ref names a reference but ref_desc is null");
+    }
+  return p;
+}
+
+// The pair table, the totals and the split of the train sets into chunks.
+// Chunks: one pair of 2000 queries is 16 workgroups on 256 compute units, so
+// the train rows are dealt to `chunks` workgroups per query tile (chunk_rows
+// each, a multiple of the staged tile and at least two tiles) until the batch
+// offers about two workgroups per unit; the partial top-2 lists merge by key,
+// so the result does not depend on the split.
+struct MatchPlan {
+  std::vector<MatchPair> pair;
+  size_t NQ = 0, NT = 0, NM = 0;      // dense records, train slots, match capacity
+  int max_nq = 0, max_nt = 0;
+  int chunks = 1, chunk_rows = kMatchTTile;
+};
+inline MatchPlan match_plan(const char* fn, const ba_match_batch* b, int unique, int first_pair, int n_pairs) {
+  MatchPlan M;
+  M.pair.resize((size_t)n_pairs);
+  size_t tiles = 0;
+  for (int i = 0; i < n_pairs; ++i) {
+    MatchPair& P = M.pair[(size_t)i];
+    const int sq = b->pair_query[first_pair + i], st = b->pair_train[first_pair + i];
+    P.q0 = b->set_offset[sq]; P.nq = b->set_offset[sq + 1] - P.q0;
+    P.t0 = b->set_offset[st]; P.nt = b->set_offset[st + 1] - P.t0;
+    P.cap = unique ? std::min(P.nq, P.nt) : P.nq;
+    P.qoff = (int)M.NQ; P.toff = (int)M.NT; P.moff = (int)M.NM;
+    M.NQ += (size_t)P.nq; M.NT += (size_t)P.nt; M.NM += (size_t)P.cap;
+    M.max_nq = std::max(M.max_nq, P.nq); M.max_nt = std::max(M.max_nt, P.nt);
+    tiles += ((size_t)P.nq + kMatchQTile - 1) / kMatchQTile;
+  }
+  if (M.NQ > 0x7fffffffull || M.NT > 0x7fffffffull)
+    throw BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + "the pairs hold more than 2^31 - 1 query or train rows"};
+  if (tiles > 0 && M.max_nt > 0) {
+    const size_t want = (512 + tiles - 1) / tiles;
+    const size_t most = ((size_t)M.max_nt + 2 * kMatchTTile - 1) / (2 * kMatchTTile);
+    M.chunks = (int)std::max<size_t>(1, std::min(want, most));
+    const int per = (M.max_nt + M.chunks - 1) / M.chunks;
+    M.chunk_rows = (per + kMatchTTile - 1) / kMatchTTile * kMatchTTile;
+    M.chunks = (M.max_nt + M.chunk_rows - 1) / M.chunk_rows;
+  }
+  return M;
+}
+
+// The staging buffer.  ba_match_descriptors (knn == false): the pair table,
+// row_ref, reference descriptors, descriptors | counts, match records | norms,
+// partial top-2 lists, dense records, survivor flags, per-train winners,
+// per-train counts.  ba_match_knn (knn == true): the same inputs | the dense
+// records | norms, partial lists.
+struct MatchLayout {
+  SectionLayout L{256};
+  size_t pair = 0, desc = 0, row_ref = 0, ref = 0;
+  size_t cnt = 0, matches = 0;
+  size_t norms = 0, part = 0, knn = 0, surv = 0, win = 0, hist = 0;
+};
+inline MatchLayout match_layout(const MatchPlan& M, size_t rows, size_t n_ref, int dim, bool have_ref, bool knn) {
+  MatchLayout P;
+  SectionLayout& L = P.L;
+  const size_t N = M.pair.size();
+  P.pair = L.add(sizeof(MatchPair) * N);
+  P.row_ref = L.add(have_ref ? sizeof(int32_t) * rows : 0); P.ref = L.add(have_ref ? sizeof(float) * n_ref * (size_t)dim : 0);
+  P.desc = L.add(sizeof(float) * rows * (size_t)dim);   // the last input: uploaded from the caller's array
+  L.end_inputs();
+  if (knn) {
+    P.knn = L.add(sizeof(ba_match_neighbors) * M.NQ);
+    L.end_outputs();
+  } else {
+    P.cnt = L.add(sizeof(int32_t) * N); P.matches = L.add(sizeof(ba_match) * M.NM);
+    L.end_outputs();
+    P.knn = L.add(sizeof(ba_match_neighbors) * M.NQ); P.surv = L.add(M.NQ);
+    P.win = L.add(sizeof(uint64_t) * M.NT); P.hist = L.add(sizeof(int32_t) * M.NT);
+  }
+  P.norms = L.add(sizeof(float) * (rows + (have_ref ? n_ref : 0)));
+  P.part = L.add(sizeof(uint64_t) * 2 * M.NQ * (size_t)M.chunks);
+  return P;
 }
 
 // One problem of ba_solve_window_batch as the kernel (ba_window.hip) reads it

@@ -457,3 +457,53 @@ def triangulation_batch(problem: Problem) -> TriangulationBatch:
         obs_offset=off.astype(np.int32), obs_cam=np.ascontiguousarray(p.obs_cam[order]),
         obs_uv=np.ascontiguousarray(p.obs_uv[order]), pts=p.pts.copy(), order=order.astype(np.int64),
         huber_a=float(p.huber_a))
+
+
+# one record of Solver.match_descriptors (ba_match, include/ba_hip.h)
+MATCH_DTYPE = np.dtype([("query", np.int32), ("train", np.int32), ("distance", np.float32),
+                        ("second_distance", np.float32), ("ref_distance", np.float32)])
+# one record of Solver.match_knn (ba_match_neighbors)
+MATCH_KNN_DTYPE = np.dtype([("idx0", np.int32), ("idx1", np.int32), ("d2_0", np.float32), ("d2_1", np.float32)])
+
+
+@dataclass
+class MatchBatch:
+    """The arrays of the C-ABI's ba_match_batch: set s owns rows
+    [set_offset[s], set_offset[s+1]) of desc; pair i matches set pairs[i, 0]
+    (queries) against set pairs[i, 1] (train)."""
+    dim: int
+    set_offset: np.ndarray         # (S + 1,) int32
+    desc: np.ndarray               # (rows, dim) float32
+    pairs: np.ndarray              # (P, 2) int32: (query set, train set)
+    row_ref: np.ndarray | None     # (rows,) int32: index into ref_desc or -1
+    ref_desc: np.ndarray | None    # (R, dim) float32
+
+
+def pack_match_batch(sets, pairs, row_ref=None, ref_desc=None, dim: int | None = None) -> MatchBatch:
+    """Descriptor sets (a list of (n_s, dim) arrays, empty ones allowed) and
+    (query set, train set) index pairs as a MatchBatch.  row_ref: per set, an
+    int array naming a row of ref_desc per descriptor (-1: none), or None for a
+    set without references.  dim is needed only when every set is empty."""
+    sets = [np.asarray(s, dtype=np.float32) for s in sets]
+    if dim is None:
+        dims = {s.shape[1] for s in sets if s.ndim == 2 and s.shape[0] > 0}
+        if ref_desc is not None and np.asarray(ref_desc).ndim == 2:
+            dims.add(np.asarray(ref_desc).shape[1])
+        if len(dims) != 1:
+            raise ValueError("pack_match_batch: the sets do not agree on one descriptor length")
+        dim = dims.pop()
+    sets = [s.reshape(-1, dim) for s in sets]
+    off = np.zeros(len(sets) + 1, np.int64)
+    np.cumsum([s.shape[0] for s in sets], out=off[1:])
+    desc = np.ascontiguousarray(np.concatenate(sets, axis=0) if sets else np.zeros((0, dim)), dtype=np.float32)
+    rr = None
+    if row_ref is not None:
+        if len(row_ref) != len(sets):
+            raise ValueError("pack_match_batch: row_ref needs one entry per set")
+        rr = np.full(int(off[-1]), -1, np.int32)
+        for s, r in enumerate(row_ref):
+            if r is not None:
+                rr[off[s]:off[s + 1]] = np.asarray(r, dtype=np.int32).reshape(-1)
+    rd = None if ref_desc is None else np.ascontiguousarray(ref_desc, dtype=np.float32).reshape(-1, dim)
+    return MatchBatch(dim=int(dim), set_offset=off.astype(np.int32), desc=desc,
+                      pairs=np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2), row_ref=rr, ref_desc=rd)

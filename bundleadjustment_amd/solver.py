@@ -13,7 +13,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as N
-from .problem import HUBER_A, Problem, WindowBatch, pack_window_batch
+from .problem import (HUBER_A, MATCH_DTYPE, MATCH_KNN_DTYPE, MatchBatch, Problem, WindowBatch, pack_match_batch,
+                      pack_window_batch)
 
 
 def _ptr(a):
@@ -709,6 +710,72 @@ class Solver:
         out = np.empty(max(n, 0))
         if n > 0:
             self.lib.ba_two_view_times(self.h, _ptr(out), n)
+        return out
+
+    # -- descriptor matching ------------------------------------------------
+    def _match_batch(self, batch: MatchBatch):
+        mb = batch
+        pq = np.ascontiguousarray(mb.pairs[:, 0])
+        pt = np.ascontiguousarray(mb.pairs[:, 1])
+        b = N.ba_match_batch(dim=int(mb.dim), n_sets=mb.set_offset.size - 1, n_pairs=mb.pairs.shape[0],
+                             n_ref=0 if mb.ref_desc is None else mb.ref_desc.shape[0], set_offset=_ptr(mb.set_offset),
+                             desc=_ptr(mb.desc), pair_query=_ptr(pq), pair_train=_ptr(pt), row_ref=_ptr(mb.row_ref),
+                             ref_desc=_ptr(mb.ref_desc))
+        return b, (pq, pt, mb)
+
+    def match_descriptors(self, sets, pairs=None, row_ref=None, ref_desc=None, **match_options
+                          ) -> tuple[np.ndarray, np.ndarray]:
+        """Batched descriptor matching (ba_match_descriptors): the exact 2-NN
+        of every query, Lowe's ratio test and the one-match-per-train filter,
+        on the device.  sets: a MatchBatch, or a list of (n_s, dim) float32
+        descriptor arrays with pairs (P, 2) of (query set, train set) indices
+        (row_ref / ref_desc: pack_match_batch).  match_options: ratio, unique,
+        max_distance (defaults: ba_match_defaults).  Returns (match_offset
+        (P + 1,) int32, matches: a MATCH_DTYPE record array); pair i owns
+        matches[match_offset[i]:match_offset[i+1]], in increasing (train,
+        query)."""
+        mb = sets if isinstance(sets, MatchBatch) else pack_match_batch(sets, pairs, row_ref, ref_desc)
+        b, _keep = self._match_batch(mb)
+        p = N.ba_match_options()
+        self.lib.ba_match_defaults(C.byref(p))
+        for key, val in match_options.items():
+            if key not in ("ratio", "unique", "max_distance"):
+                raise TypeError(f"match_descriptors: unknown option {key!r}")
+            setattr(p, key, int(val) if key == "unique" else float(val))
+        cap = 0
+        if mb.pairs.size and mb.set_offset.size > 1:      # (a bad index or offset is the library's to report)
+            n = np.maximum(np.diff(mb.set_offset.astype(np.int64)), 0)
+            nq, nt = (n[np.clip(mb.pairs[:, k], 0, n.size - 1)] for k in (0, 1))
+            cap = int((np.minimum(nq, nt) if p.unique else nq).sum())
+        off = np.zeros(mb.pairs.shape[0] + 1, np.int32)
+        out = np.zeros(max(cap, 1), MATCH_DTYPE)
+        self._check(self.lib.ba_match_descriptors(self.h, C.byref(b), C.byref(p), _ptr(off), _ptr(out)),
+                    "ba_match_descriptors")
+        return off, out[:int(off[-1])].copy()
+
+    def match_knn(self, sets, pairs=None, pair: int = 0) -> np.ndarray:
+        """The dense 2-NN record of every query of one pair exactly as
+        match_descriptors forms it, before any filtering (ba_match_knn): a
+        MATCH_KNN_DTYPE record array (index -1 and d2 = inf: no neighbour)."""
+        mb = sets if isinstance(sets, MatchBatch) else pack_match_batch(sets, pairs)
+        b, _keep = self._match_batch(mb)
+        nq = 0
+        if 0 <= int(pair) < mb.pairs.shape[0]:
+            s = int(mb.pairs[int(pair), 0])
+            if 0 <= s < mb.set_offset.size - 1:
+                nq = int(mb.set_offset[s + 1] - mb.set_offset[s])
+        out = np.zeros(max(nq, 1), MATCH_KNN_DTYPE)
+        self._check(self.lib.ba_match_knn(self.h, C.byref(b), int(pair), _ptr(out)), "ba_match_knn")
+        return out[:nq].copy()
+
+    def match_times(self) -> np.ndarray:
+        """Times (ms) of the last match_descriptors: host preparation (wall),
+        the kernels (device), the whole call (wall), then the kernels' phases:
+        norms, the 2-NN contraction, merge / ratio / unique / compaction."""
+        n = self.lib.ba_match_times(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            self.lib.ba_match_times(self.h, _ptr(out), n)
         return out
 
     def synchronize(self):

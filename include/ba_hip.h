@@ -786,6 +786,118 @@ int ba_two_view_hypotheses_e5(ba_ctx* ctx, const ba_two_view_batch* batch, const
                               int n, int32_t* sample /* [8*n] */, int32_t* n_sol /* [n] */, double* E /* [n][10][9] */,
                               int32_t* count /* [n][10] */);
 
+/* ---------------------------------------------------------------------------
+ * ba_match_descriptors: batched descriptor matching on the device: exact
+ * 2-nearest-neighbour search, Lowe's ratio test and the one-match-per-train
+ * filter.  This is the reference's FeatureProcessor::matchFeatures
+ * (FeatureProcessor.cpp:39-95: FLANN knnMatch(k = 2), ratio 0.7, sort by
+ * trainIdx and keep the first of each run), which feeds every geometric entry
+ * above.  FLANN's randomised kd-trees are approximate and unseeded; the exact
+ * brute-force answer is what they approximate, and it is what is pinned here
+ * (csrc/ba_match.h is the text, the same on the device and in host programs).
+ *
+ * Batch.  n_sets descriptor sets in CSR form: set s owns rows
+ * [set_offset[s], set_offset[s+1]) of desc (row-major, dim floats per row,
+ * dim 64 or 128).  Pair i matches the rows of set pair_query[i] (the queries)
+ * against those of set pair_train[i]; a set may appear in any number of pairs
+ * and is uploaded once.  Match indices are local to their sets.  Optional
+ * association input: row_ref[r] >= 0 names a reference descriptor
+ * ref_desc[row_ref[r]] of row r (the map point's own descriptor); -1 is none.
+ * Descriptors are expected finite.
+ *
+ * Distance (float32 throughout).
+ *   dot(q, t) = the chain acc = fmaf(q_k, t_k, acc), k = 0 .. dim-1 ascending, from 0
+ *   nrm(x)    = dot(x, x)
+ *   x         = fmaf(-2, dot(q, t), nrm(q) + nrm(t))      (the sum rounded first)
+ *   d2        = x > 0 ? x : 0
+ *   distance  = (float)sqrt((double)d2)                   (the correctly rounded float root)
+ * A descriptor against itself gives exactly 0.
+ *
+ * 2-NN.  Per query the two smallest keys (bits(d2) << 32 | train) over the
+ * train set (d2 >= 0, so its bit pattern orders like its value; ties go to the
+ * lower train index).  Partial lists merge exactly under that order, so the
+ * result does not depend on tiling or on how a pair is split over workgroups.
+ * A missing neighbour has index -1 and d2 = +inf.
+ *
+ * Ratio.  A query with two neighbours survives when
+ *   distance0 < ratio * distance1   (a float product, rounded once)   and
+ *   distance0 <= max_distance.
+ * A pair whose train set has fewer than two rows yields no matches (the
+ * reference indexes knn_matches[i][1] unguarded there).
+ *
+ * Unique train (unique = 1).  Per train index the surviving query of smallest
+ * (bits(d2_0) << 32 | query) wins (the reference's std::sort is unstable, so
+ * which query it keeps is unspecified).  unique = 0 returns every survivor.
+ *
+ * Output.  Pair i owns matches [match_offset[i], match_offset[i+1]) in
+ * increasing (train, query): the order the reference returns.  `matches`
+ * must hold the sum over the pairs of min(n_q, n_t) records with unique = 1,
+ * of n_q with unique = 0.  ref_distance: for a query row with a reference
+ * descriptor, the distance (same formulas) from the match's *train*
+ * descriptor to that reference (the test of BundleAdjustment.cpp:135-137; the
+ * threshold stays with the caller); -1 without one.
+ *
+ * Contract, as ba_two_view_ransac: a pair's output bits depend only on its own
+ * data and the options, not on its place in the batch or on the other pairs;
+ * two calls give bitwise equal output; the only atomics are integer minima
+ * and counts; the context's current problem is untouched; no collective; the
+ * call blocks until the results are on the host.  Empty sets and an empty
+ * batch are valid.
+ *
+ * Errors (the context stays usable; nothing is launched; all validation is on
+ * the host):
+ *   BA_ERR_INVALID_ARGUMENT  a NULL required array, dim other than 64 / 128,
+ *                            negative counts, set_offset[0] != 0 or a
+ *                            decreasing set_offset (the message names the
+ *                            set), a pair's set index out of range, a row_ref
+ *                            outside -1 .. n_ref-1, a set of more than
+ *                            8388480 rows, a ratio that is negative or not
+ *                            finite, a max_distance that is negative or NaN,
+ *                            unique other than 0 / 1, reserved != 0,
+ *   BA_ERR_OUT_OF_MEMORY     the scratch cannot be allocated. */
+typedef struct {
+  int32_t dim;                   /* 64 or 128 */
+  int32_t n_sets, n_pairs, n_ref;
+  const int32_t* set_offset;     /* [n_sets+1], [0] = 0, non-decreasing: rows of desc */
+  const float*   desc;           /* [rows * dim] */
+  const int32_t* pair_query;     /* [n_pairs] set index of the queries */
+  const int32_t* pair_train;     /* [n_pairs] set index of the train rows */
+  const int32_t* row_ref;        /* [rows] index into ref_desc or -1; NULL = none */
+  const float*   ref_desc;       /* [n_ref * dim]; may be NULL when no row_ref is >= 0 */
+} ba_match_batch;
+
+typedef struct {
+  float   ratio;                 /* default 0.7f (FeatureProcessor.cpp:58) */
+  int32_t unique;                /* default 1 */
+  float   max_distance;          /* default +inf */
+  int32_t reserved;              /* 0 */
+} ba_match_options;
+
+typedef struct {
+  int32_t query, train;          /* local row indices of the pair's two sets */
+  float   distance, second_distance;
+  float   ref_distance;          /* -1 without a reference descriptor */
+} ba_match;
+
+typedef struct {                 /* ba_match_knn: one query, before any filtering */
+  int32_t idx0, idx1;            /* -1: none */
+  float   d2_0, d2_1;            /* squared distances; +inf: none */
+} ba_match_neighbors;
+
+void ba_match_defaults(ba_match_options* opt);
+int ba_match_descriptors(ba_ctx* ctx, const ba_match_batch* batch, const ba_match_options* opt /* NULL = defaults */,
+                         int32_t* match_offset /* [n_pairs+1] */, ba_match* matches /* capacity: see Output */);
+/* Times (ms) of the last successful ba_match_descriptors: [0] host
+ * preparation, [1] the kernels (device), [2] the whole call, then the phases
+ * of [1]: [3] norms, [4] the 2-NN contraction, [5] merge, ratio, unique filter
+ * and compaction.  As ba_pnp_times otherwise. */
+int ba_match_times(ba_ctx* ctx, double* ms, int n);
+/* Test / inspection entry point, in the role of ba_two_view_hypotheses: the
+ * dense 2-NN record of every query of pair `pair` exactly as
+ * ba_match_descriptors forms it, before the ratio test.  Same errors as
+ * ba_match_descriptors (no options are read), plus a pair out of range. */
+int ba_match_knn(ba_ctx* ctx, const ba_match_batch* batch, int pair, ba_match_neighbors* out /* [n_q of the pair] */);
+
 /* Test / inspection entry point: the state inside ceres::Solve's
  * SchurComplementSolver (Optimizer.cpp:242, DENSE_SCHUR) for one step.
  * Linearises at the current parameters with iteration-0 Jacobi scaling, then
