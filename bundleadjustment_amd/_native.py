@@ -200,6 +200,63 @@ class ba_match_neighbors(C.Structure):
     _fields_ = [("idx0", C.c_int32), ("idx1", C.c_int32), ("d2_0", C.c_float), ("d2_1", C.c_float)]
 
 
+class ba_map_point_batch(C.Structure):
+    _fields_ = [
+        ("dim", C.c_int32), ("n_cams", C.c_int32), ("n_pts", C.c_int32), ("n_rows", C.c_int32),
+        ("cam_center", C.c_void_p), ("pts", C.c_void_p), ("obs_offset", C.c_void_p), ("obs_cam", C.c_void_p),
+        ("obs_row", C.c_void_p), ("obs_scale", C.c_void_p), ("ref_obs", C.c_void_p), ("desc", C.c_void_p),
+    ]
+
+
+class ba_map_point_options(C.Structure):
+    _fields_ = [("median_rule", C.c_int32), ("reserved", C.c_int32), ("max_scale", C.c_float), ("reserved_f", C.c_float)]
+
+
+class ba_map_point(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("best", C.c_int32), ("median", C.c_float), ("view_dir", C.c_float * 3),
+        ("min_dist", C.c_float), ("max_dist", C.c_float),
+    ]
+
+
+BA_MP_MAX_TRACK = 1024
+MP_OK, MP_EMPTY = range(2)                        # ba_mp_status
+MP_MEDIAN_REFERENCE, MP_MEDIAN_FLOAT = range(2)   # ba_mp_median
+
+
+class ba_assoc_batch(C.Structure):
+    _fields_ = [
+        ("dim", C.c_int32), ("n_cams", C.c_int32), ("n_pts", C.c_int32), ("n_rows", C.c_int32), ("n_items", C.c_int32),
+        ("n_fuse", C.c_int32),
+        ("extr", C.c_void_p), ("cam_center", C.c_void_p), ("K", C.c_void_p), ("image_size", C.c_void_p),
+        ("pts", C.c_void_p), ("pt_view_dir", C.c_void_p), ("pt_dist", C.c_void_p), ("pt_desc", C.c_void_p),
+        ("desc", C.c_void_p), ("item_cam", C.c_void_p), ("item_pt", C.c_void_p), ("item_uv", C.c_void_p),
+        ("item_scale", C.c_void_p), ("item_row", C.c_void_p), ("item_cur_row", C.c_void_p), ("fuse_pairs", C.c_void_p),
+    ]
+
+
+class ba_assoc_options(C.Structure):
+    _fields_ = [
+        ("chi2", C.c_float), ("min_cos", C.c_float), ("max_desc_dist", C.c_float), ("fuse_min_cos", C.c_float),
+        ("fuse_max_desc_dist", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
+class ba_assoc_result(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("chi", C.c_float), ("cosine", C.c_float), ("world_dist", C.c_float),
+        ("dist_matched", C.c_float), ("dist_current", C.c_float),
+    ]
+
+
+class ba_fuse_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("cosine", C.c_float), ("dist", C.c_float)]
+
+
+(AS_ADD, AS_REPLACE, AS_BEHIND, AS_BOUNDS, AS_CHI2, AS_ANGLE, AS_DEPTH, AS_DESC, AS_WORSE) = range(9)   # ba_assoc_status
+FUSE_OK, FUSE_ANGLE, FUSE_DESC = range(3)                                                              # ba_fuse_status
+
+
 class ba_covariance_request(C.Structure):
     _fields_ = [
         ("n_cam_pairs", C.c_int32), ("n_points", C.c_int32), ("cam_pairs", C.c_void_p), ("cam_cov", C.c_void_p),
@@ -286,6 +343,14 @@ SIGNATURES = [
                                        C.c_void_p]),
     ("ba_match_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("ba_match_knn", C.c_int, [C.c_void_p, C.POINTER(ba_match_batch), C.c_int, C.c_void_p]),
+    ("ba_map_points_defaults", None, [C.POINTER(ba_map_point_options)]),
+    ("ba_map_points_update", C.c_int, [C.c_void_p, C.POINTER(ba_map_point_batch), C.POINTER(ba_map_point_options),
+                                       C.c_void_p, C.c_void_p]),
+    ("ba_map_points_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ba_map_points_distances", C.c_int, [C.c_void_p, C.POINTER(ba_map_point_batch), C.c_int, C.c_void_p, C.c_void_p]),
+    ("ba_associate_defaults", None, [C.POINTER(ba_assoc_options)]),
+    ("ba_associate", C.c_int, [C.c_void_p, C.POINTER(ba_assoc_batch), C.POINTER(ba_assoc_options), C.c_void_p,
+                               C.c_void_p]),
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
     ("ba_covariance_ex", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request_ex)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

@@ -454,6 +454,46 @@ struct MatchArgs {
 // ev: three events recorded after the norms, the 2-NN and the selection (null: none)
 void launch_match(const MatchArgs& A, hipStream_t s, hipEvent_t* ev);
 
+// map-point upkeep: representative descriptor, viewing direction, depth bounds (ba_map_points.hip)
+struct MapPointsArgs {
+  int dim, median_rule;
+  float max_scale;
+  int first[3], count[3];          // MapPointsPlan: the tiers of `order`
+  // inputs
+  const float* center;             // [n_cams][3]
+  const float* pts;                // [n_pts][3]
+  const int* obs_offset;           // [n_pts + 1]
+  const int* obs_cam;              // [n_obs]
+  const int* obs_row;              // [n_obs]
+  const float* obs_scale;          // [n_obs] or null (all 1)
+  const int* ref_obs;              // [n_pts] or null (all 0)
+  const float* desc;               // [n_rows][dim]
+  const int* order;                // the points of the launch, tier by tier
+  // outputs
+  ba_map_point* out;               // record of point p at out[p * out_stride] (0: the one inspected point)
+  int out_stride;
+  float* desc_out;                 // [n_pts][dim] or null
+  float* dbg_D;                    // ba_map_points_distances: [n][n] and [n] of the one point; null otherwise
+  float* dbg_m;
+};
+void launch_map_points(const MapPointsArgs& A, hipStream_t s);
+
+// the gates of searchInNeighbors per item and per fuse pair (ba_map_points.hip)
+struct AssocArgs {
+  int dim, n_items, n_fuse;
+  ba_assoc_options opt;
+  const float *extr, *center, *K;
+  const int* image_size;
+  const float *pts, *pt_view_dir, *pt_dist, *pt_desc, *desc;
+  const int *item_cam, *item_pt;
+  const float *item_uv, *item_scale;   // item_scale may be null (all 1)
+  const int *item_row, *item_cur_row;  // item_cur_row may be null (none)
+  const int* fuse_pairs;
+  ba_assoc_result* items;
+  ba_fuse_result* fuse;
+};
+void launch_associate(const AssocArgs& A, hipStream_t s);
+
 int grid_for(int n);
 int pt_group_grid(int np);   // grid of the kPtLanes-lanes-per-point kernels
 

@@ -110,9 +110,10 @@ struct ba_ctx {
   unsigned* d_ticket = nullptr;  // k_reduce<true>'s last-workgroup ticket (zero between launches)
   unsigned scal_seq = 0;
   // staging of ba_solve_pose_batch, ba_solve_window_batch, ba_triangulate,
-  // ba_pnp_ransac, ba_two_view_ransac and ba_match_descriptors (one each: a
-  // call of one never makes another reallocate)
-  StagingArena pose, win, tri, pnp, tv, match;
+  // ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors and
+  // ba_map_points_update / ba_associate (one each: a call of one never makes
+  // another reallocate)
+  StagingArena pose, win, tri, pnp, tv, match, mp;
   // ba_solve_window_batch: the last call's logs and times
   std::vector<ba_iteration> win_log;   // [n_problems][win_log_cap]
   std::vector<int> win_log_n;
@@ -122,6 +123,7 @@ struct ba_ctx {
   std::vector<double> pnp_ms;          // ba_pnp_times of the last call
   std::vector<double> tv_ms;           // ba_two_view_times of the last call
   std::vector<double> match_ms;        // ba_match_times of the last call
+  std::vector<double> mp_ms;           // ba_map_points_times of the last call
   hipEvent_t match_ev[3] = {nullptr, nullptr, nullptr};   // phase stamps of ba_match_descriptors (created by its first call)
 
   // host copies of the sorted structure, kept for the lazily built
@@ -2081,7 +2083,7 @@ int ba_destroy(ba_ctx* ctx) {
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
-  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv, &ctx->match}) (void)hipFree(a->dev);
+  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv, &ctx->match, &ctx->mp}) (void)hipFree(a->dev);
   for (hipEvent_t e : ctx->match_ev) if (e) (void)hipEventDestroy(e);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -2989,6 +2991,167 @@ int ba_match_knn(ba_ctx* ctx, const ba_match_batch* b, int pair, ba_match_neighb
                           ctx->stream));
     HIP_OK(hipStreamSynchronize(ctx->stream));
     std::memcpy(out, h.data() + P.knn, sizeof(ba_match_neighbors) * M.NQ);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// ba_map_points_update / ba_map_points_distances / ba_associate: host side.
+// Validation, the tier plan and the section layouts are plain C++
+// (check_map_points, map_points_plan, check_assoc: host/ba_batch_pack.hpp);
+// the tables go up through the staging copy and the descriptors from the
+// caller's array, then the launches of ba_map_points.hip and one download.
+// The context's current problem is not touched.
+// ---------------------------------------------------------------------------
+void ba_map_points_defaults(ba_map_point_options* opt) {
+  if (opt) map_points_defaults(*opt);
+}
+void ba_associate_defaults(ba_assoc_options* opt) {
+  if (opt) assoc_defaults(*opt);
+}
+
+namespace {
+
+MapPointsArgs map_points_stage(ba_ctx* ctx, const ba_map_point_batch* b, const ba_map_point_options& p,
+                               const MapPointsPlan& M, const MapPointsLayout& P, const std::string& fn) {
+  const size_t np = (size_t)b->n_pts, no = (size_t)b->obs_offset[np], dim = (size_t)b->dim;
+  HIP_OK(hipSetDevice(ctx->device));
+  ctx->mp.reserve(ctx, P.L.total, fn);
+  std::vector<char>& h = ctx->mp.host;
+  h.resize(P.L.io_b);
+  std::memset(h.data(), 0, P.desc);
+  stage(h, P.center, b->cam_center, sizeof(float) * 3 * (size_t)b->n_cams);
+  stage(h, P.pts, b->pts, sizeof(float) * 3 * np);
+  stage(h, P.off, b->obs_offset, sizeof(int32_t) * (np + 1));
+  stage(h, P.cam, b->obs_cam, sizeof(int32_t) * no);
+  stage(h, P.row, b->obs_row, sizeof(int32_t) * no);
+  if (b->obs_scale) stage(h, P.scale, b->obs_scale, sizeof(float) * no);
+  if (b->ref_obs) stage(h, P.ref, b->ref_obs, sizeof(int32_t) * np);
+  stage(h, P.order, M.order.data(), sizeof(int32_t) * M.order.size());
+  char* d = ctx->mp.dev;
+  HIP_OK(hipMemcpyAsync(d, h.data(), P.desc, hipMemcpyHostToDevice, ctx->stream));
+  // the descriptors are the bulk of the batch: they go up from the caller's array, which the call outlives
+  if (b->n_rows > 0 && no > 0)
+    HIP_OK(hipMemcpyAsync(d + P.desc, b->desc, sizeof(float) * (size_t)b->n_rows * dim, hipMemcpyHostToDevice, ctx->stream));
+  MapPointsArgs A{};
+  A.dim = b->dim; A.median_rule = p.median_rule; A.max_scale = p.max_scale;
+  for (int t = 0; t < 3; ++t) { A.first[t] = M.first[t]; A.count[t] = M.count[t]; }
+  A.center = at<const float>(d, P.center); A.pts = at<const float>(d, P.pts); A.obs_offset = at<const int>(d, P.off);
+  A.obs_cam = at<const int>(d, P.cam); A.obs_row = at<const int>(d, P.row);
+  A.obs_scale = b->obs_scale ? at<const float>(d, P.scale) : nullptr;
+  A.ref_obs = b->ref_obs ? at<const int>(d, P.ref) : nullptr;
+  A.desc = at<const float>(d, P.desc); A.order = at<const int>(d, P.order);
+  A.out = at<ba_map_point>(d, P.out); A.out_stride = 1;
+  return A;
+}
+
+}  // namespace
+
+int ba_map_points_update(ba_ctx* ctx, const ba_map_point_batch* b, const ba_map_point_options* opt, ba_map_point* out,
+                         float* desc_out) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_map_points_update: ";
+    const ba_map_point_options p = check_map_points(fn.c_str(), b, opt);
+    const size_t np = (size_t)b->n_pts, dim = (size_t)b->dim;
+    if (np == 0) return;
+    if (!out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const double t0 = now_s();
+    const MapPointsPlan M = map_points_plan(b, 0, b->n_pts);
+    const MapPointsLayout P = map_points_layout(b, np, desc_out != nullptr, 0);
+    MapPointsArgs A = map_points_stage(ctx, b, p, M, P, fn);
+    A.desc_out = desc_out ? at<float>(ctx->mp.dev, P.desc_out) : nullptr;
+    const double t_prep = now_s() - t0;
+    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
+    launch_map_points(A, ctx->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
+    std::vector<char>& h = ctx->mp.host;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, ctx->mp.dev + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    float kernel_ms = 0.0f;
+    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
+    std::memcpy(out, h.data() + P.out, sizeof(ba_map_point) * np);
+    if (desc_out) std::memcpy(desc_out, h.data() + P.desc_out, sizeof(float) * np * dim);
+    ctx->mp_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * (now_s() - t0)};
+  });
+}
+
+int ba_map_points_times(ba_ctx* ctx, double* ms, int n) {
+  return ctx ? copy_times(ctx->mp_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
+}
+
+int ba_map_points_distances(ba_ctx* ctx, const ba_map_point_batch* b, int point, float* D, float* m) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_map_points_distances: ";
+    ba_map_point_options p = check_map_points(fn.c_str(), b, nullptr);
+    if (point < 0 || point >= b->n_pts)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "point " + std::to_string(point) + " out of range"};
+    const size_t n = (size_t)(b->obs_offset[point + 1] - b->obs_offset[point]);
+    if (n == 0) return;
+    if (!D || !m) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const MapPointsPlan M = map_points_plan(b, point, 1);
+    const MapPointsLayout P = map_points_layout(b, 1, false, n);
+    MapPointsArgs A = map_points_stage(ctx, b, p, M, P, fn);
+    A.out_stride = 0;
+    A.dbg_D = at<float>(ctx->mp.dev, P.dbg_D); A.dbg_m = at<float>(ctx->mp.dev, P.dbg_m);
+    launch_map_points(A, ctx->stream);
+    HIP_OK(hipGetLastError());
+    std::vector<char>& h = ctx->mp.host;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, ctx->mp.dev + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(D, h.data() + P.dbg_D, sizeof(float) * n * n);
+    std::memcpy(m, h.data() + P.dbg_m, sizeof(float) * n);
+  });
+}
+
+int ba_associate(ba_ctx* ctx, const ba_assoc_batch* b, const ba_assoc_options* opt, ba_assoc_result* items,
+                 ba_fuse_result* fuse) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_associate: ";
+    const ba_assoc_options p = check_assoc(fn.c_str(), b, opt);
+    const size_t nc = (size_t)b->n_cams, np = (size_t)b->n_pts, ni = (size_t)b->n_items, nf = (size_t)b->n_fuse,
+                 dim = (size_t)b->dim;
+    if (ni + nf == 0) return;
+    if ((ni > 0 && !items) || (nf > 0 && !fuse)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    if (ni + nf > 0x7fffffffull) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "more than 2^31 - 1 items and fuse pairs"};
+    const AssocLayout P = assoc_layout(b);
+    HIP_OK(hipSetDevice(ctx->device));
+    ctx->mp.reserve(ctx, P.L.total, fn);
+    std::vector<char>& h = ctx->mp.host;
+    h.resize(P.L.io_b);
+    std::memset(h.data(), 0, P.pt_desc);
+    auto put = [&](size_t off, const void* src, size_t nb) { if (src) stage(h, off, src, nb); };
+    put(P.extr, b->extr, sizeof(float) * 16 * nc); put(P.center, b->cam_center, sizeof(float) * 3 * nc);
+    put(P.K, b->K, sizeof(float) * 9 * nc); put(P.size, b->image_size, sizeof(int32_t) * 2 * nc);
+    put(P.pts, b->pts, sizeof(float) * 3 * np); put(P.dir, b->pt_view_dir, sizeof(float) * 3 * np);
+    put(P.dist, b->pt_dist, sizeof(float) * 2 * np); put(P.cam, b->item_cam, sizeof(int32_t) * ni);
+    put(P.pt, b->item_pt, sizeof(int32_t) * ni); put(P.uv, b->item_uv, sizeof(float) * 2 * ni);
+    put(P.scale, b->item_scale, sizeof(float) * ni); put(P.row, b->item_row, sizeof(int32_t) * ni);
+    put(P.cur, b->item_cur_row, sizeof(int32_t) * ni); put(P.fuse, b->fuse_pairs, sizeof(int32_t) * 2 * nf);
+    char* d = ctx->mp.dev;
+    if (P.pt_desc) HIP_OK(hipMemcpyAsync(d, h.data(), P.pt_desc, hipMemcpyHostToDevice, ctx->stream));
+    // the two descriptor tables go up from the caller's arrays, which the call outlives
+    if (np > 0 && b->pt_desc)
+      HIP_OK(hipMemcpyAsync(d + P.pt_desc, b->pt_desc, sizeof(float) * np * dim, hipMemcpyHostToDevice, ctx->stream));
+    if (b->n_rows > 0 && b->desc)
+      HIP_OK(hipMemcpyAsync(d + P.desc, b->desc, sizeof(float) * (size_t)b->n_rows * dim, hipMemcpyHostToDevice, ctx->stream));
+    AssocArgs A{};
+    A.dim = b->dim; A.n_items = b->n_items; A.n_fuse = b->n_fuse; A.opt = p;
+    A.extr = at<const float>(d, P.extr); A.center = at<const float>(d, P.center); A.K = at<const float>(d, P.K);
+    A.image_size = at<const int>(d, P.size); A.pts = at<const float>(d, P.pts); A.pt_view_dir = at<const float>(d, P.dir);
+    A.pt_dist = at<const float>(d, P.dist); A.pt_desc = at<const float>(d, P.pt_desc); A.desc = at<const float>(d, P.desc);
+    A.item_cam = at<const int>(d, P.cam); A.item_pt = at<const int>(d, P.pt); A.item_uv = at<const float>(d, P.uv);
+    A.item_scale = b->item_scale ? at<const float>(d, P.scale) : nullptr; A.item_row = at<const int>(d, P.row);
+    A.item_cur_row = b->item_cur_row ? at<const int>(d, P.cur) : nullptr; A.fuse_pairs = at<const int>(d, P.fuse);
+    A.items = at<ba_assoc_result>(d, P.items); A.fuse = at<ba_fuse_result>(d, P.fused);
+    launch_associate(A, ctx->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    if (ni) std::memcpy(items, h.data() + P.items, sizeof(ba_assoc_result) * ni);
+    if (nf) std::memcpy(fuse, h.data() + P.fused, sizeof(ba_fuse_result) * nf);
   });
 }
 

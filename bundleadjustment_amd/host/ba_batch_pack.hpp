@@ -1,7 +1,7 @@
 // ba_batch_pack.hpp — host-only packing shared by the batch entry points of
 // ba_solver.hip: the error type, the section layout of a staging buffer, the
 // CSR-offset validation, the summary record, the validation and layout of
-// ba_pnp_ransac, ba_two_view_ransac and ba_match_descriptors, and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
+// ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors, ba_map_points_update and ba_associate, and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
 // plain C++17 without a HIP header and runs under ASan + UBSan
 // (tests/cpp/batch_pack.cpp, `make -C tests/cpp sanitize`).
 #pragma once
@@ -338,6 +338,150 @@ inline MatchLayout match_layout(const MatchPlan& M, size_t rows, size_t n_ref, i
   }
   P.norms = L.add(sizeof(float) * (rows + (have_ref ? n_ref : 0)));
   P.part = L.add(sizeof(uint64_t) * 2 * M.NQ * (size_t)M.chunks);
+  return P;
+}
+
+// ---------------------------------------------------------------------------
+// ba_map_points_update / ba_map_points_distances / ba_associate
+// ---------------------------------------------------------------------------
+inline void map_points_defaults(ba_map_point_options& o) {
+  o.median_rule = BA_MP_MEDIAN_REFERENCE; o.reserved = 0; o.max_scale = 3.5831808f; o.reserved_f = 0.0f;
+}
+inline void assoc_defaults(ba_assoc_options& o) {
+  o.chi2 = 5.991f; o.min_cos = 0.5f; o.max_desc_dist = 0.2f; o.fuse_min_cos = 0.0f; o.fuse_max_desc_dist = 0.3f;
+  o.reserved = 0;
+}
+
+// Everything the kernels index with or branch on, checked on the host; the
+// options are returned with the defaults applied.
+inline ba_map_point_options check_map_points(const char* fn, const ba_map_point_batch* b, const ba_map_point_options* opt) {
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what}; };
+  if (!b || b->n_cams < 0 || b->n_pts < 0 || b->n_rows < 0) throw invalid("bad batch");
+  if (b->dim != 64 && b->dim != 128) throw invalid("dim " + std::to_string(b->dim) + " is neither 64 nor 128");
+  ba_map_point_options p;
+  if (opt) p = *opt; else map_points_defaults(p);
+  if (p.median_rule != BA_MP_MEDIAN_REFERENCE && p.median_rule != BA_MP_MEDIAN_FLOAT)
+    throw invalid("unknown median_rule " + std::to_string(p.median_rule));
+  if (!(p.max_scale > 0.0f && p.max_scale <= std::numeric_limits<float>::max()))
+    throw invalid("max_scale must be positive and finite");
+  if (p.reserved != 0 || p.reserved_f != 0.0f) throw invalid("reserved must be 0");
+  const int np = b->n_pts;
+  if (np == 0) return p;
+  if (!b->obs_offset || !b->pts) throw invalid("null array");
+  check_offsets(fn, "obs_offset", b->obs_offset, np, "point");
+  const int no = b->obs_offset[np];
+  if (no > 0 && (!b->obs_cam || !b->obs_row || !b->cam_center || !b->desc)) throw invalid("null array");
+  for (int q = 0; q < np; ++q) {
+    const int n = b->obs_offset[q + 1] - b->obs_offset[q];
+    if (n > BA_MP_MAX_TRACK)
+      throw invalid("point " + std::to_string(q) + " has a track of " + std::to_string(n) + " observations, more than " +
+                    std::to_string(BA_MP_MAX_TRACK));
+    if (b->ref_obs && n > 0 && (b->ref_obs[q] < 0 || b->ref_obs[q] >= n))
+      throw invalid("ref_obs[" + std::to_string(q) + "] out of range");
+  }
+  for (int o = 0; o < no; ++o) {
+    if (b->obs_cam[o] < 0 || b->obs_cam[o] >= b->n_cams) throw invalid("obs_cam[" + std::to_string(o) + "] out of range");
+    if (b->obs_row[o] < 0 || b->obs_row[o] >= b->n_rows) throw invalid("obs_row[" + std::to_string(o) + "] out of range");
+  }
+  return p;
+}
+
+// Points sorted into tiers by track length, so that a point takes the lanes
+// and the LDS its track needs: up to kMpShort observations a group of 16
+// lanes, up to kMpWave a wave, longer tracks a workgroup.  order lists the
+// points tier by tier, each tier in batch order; the kernels write a point's
+// record at its own index, and a point's bits do not depend on its tier.
+constexpr int kMpShort = 16, kMpWave = 64;
+struct MapPointsPlan {
+  std::vector<int32_t> order;
+  int first[3] = {0, 0, 0}, count[3] = {0, 0, 0};
+};
+inline int map_points_tier(int n) { return n <= kMpShort ? 0 : n <= kMpWave ? 1 : 2; }
+inline MapPointsPlan map_points_plan(const ba_map_point_batch* b, int first_pt, int n_pts) {
+  MapPointsPlan M;
+  M.order.resize((size_t)n_pts);
+  for (int i = 0; i < n_pts; ++i) ++M.count[map_points_tier(b->obs_offset[first_pt + i + 1] - b->obs_offset[first_pt + i])];
+  M.first[1] = M.count[0]; M.first[2] = M.count[0] + M.count[1];
+  int next[3] = {M.first[0], M.first[1], M.first[2]};
+  for (int i = 0; i < n_pts; ++i)
+    M.order[(size_t)next[map_points_tier(b->obs_offset[first_pt + i + 1] - b->obs_offset[first_pt + i])]++] = first_pt + i;
+  return M;
+}
+
+// The staging buffer of ba_map_points_update (dbg_n == 0): the tables, then
+// the descriptors | the records, the chosen descriptors.  ba_map_points_distances
+// (dbg_n = the point's track length): the same inputs | one record, D, m.
+struct MapPointsLayout {
+  SectionLayout L{256};
+  size_t center = 0, pts = 0, off = 0, cam = 0, row = 0, scale = 0, ref = 0, order = 0, desc = 0;
+  size_t out = 0, desc_out = 0, dbg_D = 0, dbg_m = 0;
+};
+inline MapPointsLayout map_points_layout(const ba_map_point_batch* b, size_t n_order, bool want_desc, size_t dbg_n) {
+  MapPointsLayout P;
+  SectionLayout& L = P.L;
+  const size_t np = (size_t)b->n_pts, no = np ? (size_t)b->obs_offset[np] : 0, dim = (size_t)b->dim;
+  P.center = L.add(sizeof(float) * 3 * (size_t)b->n_cams); P.pts = L.add(sizeof(float) * 3 * np);
+  P.off = L.add(sizeof(int32_t) * (np + 1)); P.cam = L.add(sizeof(int32_t) * no); P.row = L.add(sizeof(int32_t) * no);
+  P.scale = L.add(b->obs_scale ? sizeof(float) * no : 0); P.ref = L.add(b->ref_obs ? sizeof(int32_t) * np : 0);
+  P.order = L.add(sizeof(int32_t) * n_order);
+  P.desc = L.add(sizeof(float) * (size_t)b->n_rows * dim);   // the last input: uploaded from the caller's array
+  L.end_inputs();
+  if (dbg_n > 0) {
+    P.out = L.add(sizeof(ba_map_point)); P.dbg_D = L.add(sizeof(float) * dbg_n * dbg_n); P.dbg_m = L.add(sizeof(float) * dbg_n);
+  } else {
+    P.out = L.add(sizeof(ba_map_point) * np); P.desc_out = L.add(want_desc ? sizeof(float) * np * dim : 0);
+  }
+  L.end_outputs();
+  return P;
+}
+
+inline ba_assoc_options check_assoc(const char* fn, const ba_assoc_batch* b, const ba_assoc_options* opt) {
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what}; };
+  if (!b || b->n_cams < 0 || b->n_pts < 0 || b->n_rows < 0 || b->n_items < 0 || b->n_fuse < 0) throw invalid("bad batch");
+  if (b->dim != 64 && b->dim != 128) throw invalid("dim " + std::to_string(b->dim) + " is neither 64 nor 128");
+  ba_assoc_options p;
+  if (opt) p = *opt; else assoc_defaults(p);
+  if (p.reserved != 0) throw invalid("reserved must be 0");
+  if (b->n_items > 0 && (!b->extr || !b->cam_center || !b->K || !b->image_size || !b->pts || !b->pt_view_dir ||
+                         !b->pt_dist || !b->pt_desc || !b->desc || !b->item_cam || !b->item_pt || !b->item_uv ||
+                         !b->item_row))
+    throw invalid("null array");
+  if (b->n_fuse > 0 && (!b->pt_view_dir || !b->pt_desc || !b->fuse_pairs)) throw invalid("null array");
+  for (int i = 0; i < b->n_items; ++i) {
+    const std::string at = "[" + std::to_string(i) + "] out of range";
+    if (b->item_cam[i] < 0 || b->item_cam[i] >= b->n_cams) throw invalid("item_cam" + at);
+    if (b->item_pt[i] < 0 || b->item_pt[i] >= b->n_pts) throw invalid("item_pt" + at);
+    if (b->item_row[i] < 0 || b->item_row[i] >= b->n_rows) throw invalid("item_row" + at);
+    if (b->item_cur_row && (b->item_cur_row[i] < -1 || b->item_cur_row[i] >= b->n_rows)) throw invalid("item_cur_row" + at);
+  }
+  for (int i = 0; i < 2 * b->n_fuse; ++i)
+    if (b->fuse_pairs[i] < 0 || b->fuse_pairs[i] >= b->n_pts)
+      throw invalid("fuse_pairs[" + std::to_string(i) + "] out of range (pair " + std::to_string(i / 2) + ")");
+  return p;
+}
+
+// The staging buffer of ba_associate: cameras, points, items, fuse pairs, the
+// two descriptor tables | item results, fuse results.
+struct AssocLayout {
+  SectionLayout L{256};
+  size_t extr = 0, center = 0, K = 0, size = 0, pts = 0, dir = 0, dist = 0, cam = 0, pt = 0, uv = 0, scale = 0, row = 0,
+         cur = 0, fuse = 0, pt_desc = 0, desc = 0;
+  size_t items = 0, fused = 0;
+};
+inline AssocLayout assoc_layout(const ba_assoc_batch* b) {
+  AssocLayout P;
+  SectionLayout& L = P.L;
+  const size_t nc = (size_t)b->n_cams, np = (size_t)b->n_pts, ni = (size_t)b->n_items, nf = (size_t)b->n_fuse, dim = (size_t)b->dim;
+  P.extr = L.add(sizeof(float) * 16 * nc); P.center = L.add(sizeof(float) * 3 * nc); P.K = L.add(sizeof(float) * 9 * nc);
+  P.size = L.add(sizeof(int32_t) * 2 * nc); P.pts = L.add(sizeof(float) * 3 * np); P.dir = L.add(sizeof(float) * 3 * np);
+  P.dist = L.add(sizeof(float) * 2 * np); P.cam = L.add(sizeof(int32_t) * ni); P.pt = L.add(sizeof(int32_t) * ni);
+  P.uv = L.add(sizeof(float) * 2 * ni); P.scale = L.add(b->item_scale ? sizeof(float) * ni : 0);
+  P.row = L.add(sizeof(int32_t) * ni); P.cur = L.add(b->item_cur_row ? sizeof(int32_t) * ni : 0);
+  P.fuse = L.add(sizeof(int32_t) * 2 * nf);
+  P.pt_desc = L.add(sizeof(float) * np * dim); P.desc = L.add(sizeof(float) * (size_t)b->n_rows * dim);
+  L.end_inputs();
+  P.items = L.add(sizeof(ba_assoc_result) * ni); P.fused = L.add(sizeof(ba_fuse_result) * nf);
+  L.end_outputs();
   return P;
 }
 

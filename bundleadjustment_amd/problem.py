@@ -507,3 +507,95 @@ def pack_match_batch(sets, pairs, row_ref=None, ref_desc=None, dim: int | None =
     rd = None if ref_desc is None else np.ascontiguousarray(ref_desc, dtype=np.float32).reshape(-1, dim)
     return MatchBatch(dim=int(dim), set_offset=off.astype(np.int32), desc=desc,
                       pairs=np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2), row_ref=rr, ref_desc=rd)
+
+
+# one record of Solver.map_points_update (ba_map_point, include/ba_hip.h)
+MAP_POINT_DTYPE = np.dtype([("status", np.int32), ("best", np.int32), ("median", np.float32), ("view_dir", np.float32, 3),
+                            ("min_dist", np.float32), ("max_dist", np.float32)])
+# the records of Solver.associate (ba_assoc_result, ba_fuse_result)
+ASSOC_DTYPE = np.dtype([("status", np.int32), ("chi", np.float32), ("cosine", np.float32), ("world_dist", np.float32),
+                        ("dist_matched", np.float32), ("dist_current", np.float32)])
+FUSE_DTYPE = np.dtype([("status", np.int32), ("cosine", np.float32), ("dist", np.float32)])
+
+
+def _f32(a, shape):
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
+
+
+def _i32(a, shape=(-1,)):
+    return np.ascontiguousarray(a, dtype=np.int32).reshape(shape)
+
+
+@dataclass
+class MapPointBatch:
+    """The arrays of the C-ABI's ba_map_point_batch: point p owns observations
+    [obs_offset[p], obs_offset[p+1]), its track in caller order."""
+    dim: int
+    cam_center: np.ndarray         # (C, 3) float32
+    pts: np.ndarray                # (P, 3) float32
+    obs_offset: np.ndarray         # (P + 1,) int32
+    obs_cam: np.ndarray            # (O,) int32
+    obs_row: np.ndarray            # (O,) int32: row of desc
+    obs_scale: np.ndarray | None   # (O,) float32
+    ref_obs: np.ndarray | None     # (P,) int32: local index within the track
+    desc: np.ndarray               # (R, dim) float32
+
+
+def pack_map_point_batch(cam_center, pts, tracks, desc, scales=None, ref_obs=None) -> MapPointBatch:
+    """tracks: per point a list of (camera, descriptor row) in the order the
+    track is to be walked; scales: per point a list of pow(1.2, octave) per
+    observation (None: all 1); ref_obs: per point the local index of the
+    reference keyframe's observation (None: 0)."""
+    desc = np.ascontiguousarray(desc, dtype=np.float32)
+    if desc.ndim != 2:
+        raise ValueError("pack_map_point_batch: desc must be (rows, dim)")
+    off = np.zeros(len(tracks) + 1, np.int64)
+    np.cumsum([len(t) for t in tracks], out=off[1:])
+    flat = np.array([o for t in tracks for o in t], np.int32).reshape(-1, 2)
+    sc = None
+    if scales is not None:
+        sc = np.array([v for t in scales for v in t], np.float32)
+        if sc.size != flat.shape[0]:
+            raise ValueError("pack_map_point_batch: scales needs one value per observation")
+    return MapPointBatch(dim=int(desc.shape[1]), cam_center=_f32(cam_center, (-1, 3)), pts=_f32(pts, (-1, 3)),
+                         obs_offset=off.astype(np.int32), obs_cam=np.ascontiguousarray(flat[:, 0]),
+                         obs_row=np.ascontiguousarray(flat[:, 1]), obs_scale=sc,
+                         ref_obs=None if ref_obs is None else _i32(ref_obs), desc=desc)
+
+
+@dataclass
+class AssocBatch:
+    """The arrays of the C-ABI's ba_assoc_batch."""
+    dim: int
+    extr: np.ndarray               # (C, 16) float32, col-major world->camera
+    cam_center: np.ndarray         # (C, 3)
+    K: np.ndarray                  # (C, 9) col-major
+    image_size: np.ndarray         # (C, 2) int32: width, height
+    pts: np.ndarray                # (P, 3)
+    pt_view_dir: np.ndarray        # (P, 3)
+    pt_dist: np.ndarray            # (P, 2): min, max
+    pt_desc: np.ndarray            # (P, dim)
+    desc: np.ndarray               # (R, dim)
+    item_cam: np.ndarray           # (I,) int32
+    item_pt: np.ndarray            # (I,) int32
+    item_uv: np.ndarray            # (I, 2)
+    item_scale: np.ndarray | None  # (I,)
+    item_row: np.ndarray           # (I,) int32
+    item_cur_row: np.ndarray | None  # (I,) int32, -1: not observed
+    fuse_pairs: np.ndarray         # (F, 2) int32
+
+
+def pack_assoc_batch(extr, cam_center, K, image_size, pts, pt_view_dir, pt_dist, pt_desc, desc, item_cam=(), item_pt=(),
+                     item_uv=(), item_row=(), item_scale=None, item_cur_row=None, fuse_pairs=()) -> AssocBatch:
+    """The snapshot that Solver.associate tests: cameras, map points (view
+    direction, depth bounds and descriptor as map_points_update returns them),
+    keypoint descriptors, the candidate items and the fuse pairs."""
+    desc = np.ascontiguousarray(desc, dtype=np.float32)
+    dim = int(desc.shape[1])
+    return AssocBatch(dim=dim, extr=_f32(extr, (-1, 16)), cam_center=_f32(cam_center, (-1, 3)), K=_f32(K, (-1, 9)),
+                      image_size=_i32(image_size, (-1, 2)), pts=_f32(pts, (-1, 3)), pt_view_dir=_f32(pt_view_dir, (-1, 3)),
+                      pt_dist=_f32(pt_dist, (-1, 2)), pt_desc=_f32(pt_desc, (-1, dim)), desc=desc,
+                      item_cam=_i32(item_cam), item_pt=_i32(item_pt), item_uv=_f32(item_uv, (-1, 2)),
+                      item_scale=None if item_scale is None else _f32(item_scale, (-1,)), item_row=_i32(item_row),
+                      item_cur_row=None if item_cur_row is None else _i32(item_cur_row),
+                      fuse_pairs=_i32(fuse_pairs, (-1, 2)))

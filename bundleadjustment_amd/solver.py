@@ -13,8 +13,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as N
-from .problem import (HUBER_A, MATCH_DTYPE, MATCH_KNN_DTYPE, MatchBatch, Problem, WindowBatch, pack_match_batch,
-                      pack_window_batch)
+from .problem import (ASSOC_DTYPE, FUSE_DTYPE, HUBER_A, MAP_POINT_DTYPE, MATCH_DTYPE, MATCH_KNN_DTYPE, AssocBatch,
+                      MapPointBatch, MatchBatch, Problem, WindowBatch, pack_match_batch, pack_window_batch)
 
 
 def _ptr(a):
@@ -777,6 +777,80 @@ class Solver:
         if n > 0:
             self.lib.ba_match_times(self.h, _ptr(out), n)
         return out
+
+    # -- map-point upkeep and association gates --------------------------------
+    def _map_point_batch(self, mb: MapPointBatch):
+        return N.ba_map_point_batch(dim=int(mb.dim), n_cams=mb.cam_center.shape[0], n_pts=mb.pts.shape[0],
+                                    n_rows=mb.desc.shape[0], cam_center=_ptr(mb.cam_center), pts=_ptr(mb.pts),
+                                    obs_offset=_ptr(mb.obs_offset), obs_cam=_ptr(mb.obs_cam), obs_row=_ptr(mb.obs_row),
+                                    obs_scale=_ptr(mb.obs_scale), ref_obs=_ptr(mb.ref_obs), desc=_ptr(mb.desc))
+
+    def map_points_update(self, batch: MapPointBatch, want_desc: bool = True, **mp_options):
+        """Map-point upkeep (ba_map_points_update): per point the
+        representative descriptor of its track, the mean viewing direction and
+        the depth bounds.  mp_options: median_rule, max_scale (defaults:
+        ba_map_points_defaults).  Returns (records: a MAP_POINT_DTYPE array,
+        desc_out (P, dim) float32 or None)."""
+        b = self._map_point_batch(batch)
+        p = N.ba_map_point_options()
+        self.lib.ba_map_points_defaults(C.byref(p))
+        for key, val in mp_options.items():
+            if key not in ("median_rule", "max_scale", "reserved", "reserved_f"):
+                raise TypeError(f"map_points_update: unknown option {key!r}")
+            setattr(p, key, float(val) if key in ("max_scale", "reserved_f") else int(val))
+        n = batch.pts.shape[0]
+        out = np.zeros(max(n, 1), MAP_POINT_DTYPE)
+        desc_out = np.zeros((max(n, 1), int(batch.dim)), np.float32) if want_desc else None
+        self._check(self.lib.ba_map_points_update(self.h, C.byref(b), C.byref(p), _ptr(out), _ptr(desc_out)),
+                    "ba_map_points_update")
+        return out[:n].copy(), (desc_out[:n].copy() if want_desc else None)
+
+    def map_points_distances(self, batch: MapPointBatch, point: int):
+        """The dense (n, n) distance matrix and the n row medians of one point
+        exactly as map_points_update forms them (ba_map_points_distances)."""
+        b = self._map_point_batch(batch)
+        n = 0
+        if 0 <= int(point) < batch.pts.shape[0]:
+            n = max(int(batch.obs_offset[int(point) + 1] - batch.obs_offset[int(point)]), 0)
+        D = np.zeros((max(n, 1), max(n, 1)), np.float32)
+        m = np.zeros(max(n, 1), np.float32)
+        self._check(self.lib.ba_map_points_distances(self.h, C.byref(b), int(point), _ptr(D), _ptr(m)),
+                    "ba_map_points_distances")
+        return D[:n, :n].copy(), m[:n].copy()
+
+    def map_points_times(self) -> np.ndarray:
+        """Times (ms) of the last map_points_update: host preparation (wall),
+        the kernels (device), the whole call (wall)."""
+        n = self.lib.ba_map_points_times(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            self.lib.ba_map_points_times(self.h, _ptr(out), n)
+        return out
+
+    def associate(self, batch: AssocBatch, **assoc_options):
+        """The gates of searchInNeighbors per candidate item and fuse pair
+        (ba_associate).  assoc_options: chi2, min_cos, max_desc_dist,
+        fuse_min_cos, fuse_max_desc_dist (defaults: ba_associate_defaults).
+        Returns (items: an ASSOC_DTYPE array, fuse: a FUSE_DTYPE array)."""
+        ab = batch
+        b = N.ba_assoc_batch(dim=int(ab.dim), n_cams=ab.extr.shape[0], n_pts=ab.pts.shape[0], n_rows=ab.desc.shape[0],
+                             n_items=ab.item_cam.shape[0], n_fuse=ab.fuse_pairs.shape[0], extr=_ptr(ab.extr),
+                             cam_center=_ptr(ab.cam_center), K=_ptr(ab.K), image_size=_ptr(ab.image_size), pts=_ptr(ab.pts),
+                             pt_view_dir=_ptr(ab.pt_view_dir), pt_dist=_ptr(ab.pt_dist), pt_desc=_ptr(ab.pt_desc),
+                             desc=_ptr(ab.desc), item_cam=_ptr(ab.item_cam), item_pt=_ptr(ab.item_pt),
+                             item_uv=_ptr(ab.item_uv), item_scale=_ptr(ab.item_scale), item_row=_ptr(ab.item_row),
+                             item_cur_row=_ptr(ab.item_cur_row), fuse_pairs=_ptr(ab.fuse_pairs))
+        p = N.ba_assoc_options()
+        self.lib.ba_associate_defaults(C.byref(p))
+        for key, val in assoc_options.items():
+            if key not in ("chi2", "min_cos", "max_desc_dist", "fuse_min_cos", "fuse_max_desc_dist", "reserved"):
+                raise TypeError(f"associate: unknown option {key!r}")
+            setattr(p, key, int(val) if key == "reserved" else float(val))
+        ni, nf = ab.item_cam.shape[0], ab.fuse_pairs.shape[0]
+        items = np.zeros(max(ni, 1), ASSOC_DTYPE)
+        fuse = np.zeros(max(nf, 1), FUSE_DTYPE)
+        self._check(self.lib.ba_associate(self.h, C.byref(b), C.byref(p), _ptr(items), _ptr(fuse)), "ba_associate")
+        return items[:ni].copy(), fuse[:nf].copy()
 
     def synchronize(self):
         self._check(self.lib.ba_synchronize(self.h), "ba_synchronize")

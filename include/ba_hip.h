@@ -898,6 +898,205 @@ int ba_match_times(ba_ctx* ctx, double* ms, int n);
  * ba_match_descriptors (no options are read), plus a pair out of range. */
 int ba_match_knn(ba_ctx* ctx, const ba_match_batch* batch, int pair, ba_match_neighbors* out /* [n_q of the pair] */);
 
+/* ---------------------------------------------------------------------------
+ * ba_map_points_update: the upkeep of every map point on the device: its
+ * representative descriptor (MapPoint::computeDescriptor, MapPoint.cpp:202-252),
+ * its mean viewing direction and its depth bounds
+ * (MapPoint::computeViewingDirection, MapPoint.cpp:166-200).  The reference
+ * runs both for every map point after every BA (SfMHelper::eraseOutlier) and
+ * on every addObservation / replaceObservation / fuse.  The outputs are what
+ * ba_prune (obs_dist), ba_match_descriptors (ref_desc) and ba_associate read.
+ * csrc/ba_map_points.h is the text, the same on the device and in host
+ * programs.
+ *
+ * Batch.  Point p owns observations [obs_offset[p], obs_offset[p+1]): its
+ * track, n observations, at most BA_MP_MAX_TRACK.  Observation o is seen by
+ * keyframe obs_cam[o] (camera centre cam_center[3 obs_cam[o]]) through the
+ * keypoint whose descriptor is row obs_row[o] of desc; a row may be named by
+ * any number of observations.  Descriptors are expected finite.
+ *
+ * Order.  The reference walks a std::map keyed by pointer, so its order is
+ * unspecified; here the order is the caller's.
+ *
+ * Distances.  D[i][j] is the distance of ba_match_descriptors between rows
+ * obs_row[i] and obs_row[j]: (float)sqrt((double)d2) with d2 = max(0,
+ * fmaf(-2, dot, nrm_i + nrm_j)) and the fmaf chains in ascending k.  D[i][i]
+ * is exactly 0; D[i][j] and D[j][i] are bitwise equal (the chain's products
+ * and the sum of the norms commute); two observations naming one row are at
+ * distance 0.
+ *
+ * Row median.  k = max(0, n/2 - 1) in integer division: the reference's
+ * curDistances[(n / 2.0) - 1] after truncation (0 for n <= 3, 1 for n = 4 and
+ * 5, 31 for n = 64 and 65).  m_i is the k-th smallest value (0-based) of row
+ * i, the self-distance included, formed by rank: the value whose key
+ * bits(D[i][j]) << 32 | j has exactly k smaller keys in the row.  The value
+ * does not depend on how ties are ordered.
+ *
+ * Choice.
+ *   BA_MP_MEDIAN_REFERENCE (default) restates the reference line for line:
+ *     t_i = (int32_t)m_i, truncated toward zero (the reference stores the
+ *     median in an int; INT32_MAX from 2^31 on), and best is the lowest i with
+ *     the smallest t_i (a strict < starting at INT_MAX).  With unit-norm SURF
+ *     rows every distance is below 2, every t_i is 0 and the reference keeps
+ *     observation 0: that is its behaviour, and the default keeps it, as
+ *     behind_rule = 0 does in ba_triangulate.
+ *   BA_MP_MEDIAN_FLOAT is what the reference's comment intends: the smallest
+ *     key bits(m_i) << 32 | i.  For n = 4 and 5 (k = 1) the median of a row is
+ *     its nearest-neighbour distance, so the two mutually nearest rows tie
+ *     bitwise and the lower index wins.
+ *   median = m_best.  With desc_out, row obs_row[best] is copied bit for bit.
+ *
+ * Viewing direction (float, round to nearest, no contraction, IEEE division
+ * and square root).  For each observation in caller order: v = X - c per
+ * component, s = (v0 v0 + v1 v1) + v2 v2, u = s > 0 ? v / sqrt(s) : v
+ * (Eigen's normalized()); sum += u per component from 0; view_dir = sum /
+ * (float)n.
+ *
+ * Depth bounds.  With r = ref_obs[p] (the reference keyframe's observation):
+ * d = sqrt((w0 w0 + w1 w1) + w2 w2), w = X - c_r (ba_prune's worldDist);
+ * max_dist = d * obs_scale[r]; min_dist = max_dist / max_scale.
+ *
+ * Empty track.  n = 0 gives BA_MP_EMPTY, best = -1 and zeros in the other
+ * fields and in the desc_out row.
+ *
+ * Contract, as ba_match_descriptors: a point's output bits depend only on its
+ * own data and the options, not on its place in the batch or on the other
+ * points (every float is formed by one thread in a fixed order and every
+ * selection is on integer keys, so the route a track length takes does not
+ * matter either); two calls give bitwise equal output; the context's current
+ * problem is untouched; no collective; the call blocks until the results are
+ * on the host.  An empty batch is valid.
+ *
+ * Errors (the context stays usable; nothing is launched; all validation is on
+ * the host):
+ *   BA_ERR_INVALID_ARGUMENT  a NULL required array, dim other than 64 / 128,
+ *                            negative counts, obs_offset[0] != 0 or a
+ *                            decreasing obs_offset (the message names the
+ *                            point), a track longer than BA_MP_MAX_TRACK, an
+ *                            obs_cam, obs_row or ref_obs out of range (the
+ *                            message names the observation or the point), an
+ *                            unknown median_rule, a max_scale that is not
+ *                            positive and finite, a non-zero reserved field,
+ *   BA_ERR_OUT_OF_MEMORY     the staging buffer cannot be allocated. */
+#define BA_MP_MAX_TRACK 1024
+enum ba_mp_status { BA_MP_OK = 0, BA_MP_EMPTY = 1 };
+enum ba_mp_median { BA_MP_MEDIAN_REFERENCE = 0, BA_MP_MEDIAN_FLOAT = 1 };
+
+typedef struct {
+  int32_t dim;                   /* 64 or 128 */
+  int32_t n_cams, n_pts, n_rows;
+  const float*   cam_center;     /* [3*n_cams] getWorldPos() (= getPose().block(0,3,3,1)) */
+  const float*   pts;            /* [3*n_pts]  MapPoint::getPosition() */
+  const int32_t* obs_offset;     /* [n_pts+1], [0] = 0, non-decreasing: point p owns its track */
+  const int32_t* obs_cam;        /* [n_obs] observing keyframe */
+  const int32_t* obs_row;        /* [n_obs] row of desc: the observing keypoint's descriptor */
+  const float*   obs_scale;      /* [n_obs] (float)pow(1.2, octave); NULL = all 1 (as ba_tri_batch) */
+  const int32_t* ref_obs;        /* [n_pts] local index, within the track, of the reference keyframe's
+                                    observation; NULL = 0 */
+  const float*   desc;           /* [n_rows*dim] row-major */
+} ba_map_point_batch;
+
+typedef struct {
+  int32_t median_rule;           /* default BA_MP_MEDIAN_REFERENCE */
+  int32_t reserved;              /* 0 */
+  float   max_scale;             /* default (float)pow(1.2, 7) = 3.5831808f */
+  float   reserved_f;            /* 0 */
+} ba_map_point_options;
+
+typedef struct {                 /* 32 bytes */
+  int32_t status, best;          /* best: local index within the track of the chosen descriptor; -1 if EMPTY */
+  float   median;                /* m_best */
+  float   view_dir[3];
+  float   min_dist, max_dist;
+} ba_map_point;
+
+void ba_map_points_defaults(ba_map_point_options* opt);
+int ba_map_points_update(ba_ctx* ctx, const ba_map_point_batch* batch, const ba_map_point_options* opt /* NULL = defaults */,
+                         ba_map_point* out /* [n_pts] */, float* desc_out /* [n_pts*dim], may be NULL */);
+/* Times (ms) of the last successful ba_map_points_update: [0] host
+ * preparation, [1] the kernels (device), [2] the whole call.  As
+ * ba_match_times otherwise. */
+int ba_map_points_times(ba_ctx* ctx, double* ms, int n);
+/* Test / inspection entry point, in the role of ba_match_knn: the dense n x n
+ * distance matrix and the n row medians of point `point`, exactly as
+ * ba_map_points_update forms them.  Same errors (no options are read), plus a
+ * point out of range. */
+int ba_map_points_distances(ba_ctx* ctx, const ba_map_point_batch* batch, int point, float* D /* [n*n] */, float* m /* [n] */);
+
+/* ---------------------------------------------------------------------------
+ * ba_associate: the gates of SfMHelper::searchInNeighbors
+ * (SfMHelper.cpp:254-479) per candidate association, as a pure function of a
+ * snapshot.  The caller keeps the object graph and the case analysis (which
+ * side of a match has a map point); the two middle branches of the reference
+ * are one test with the roles swapped, so an item is (camera, keypoint, map
+ * point) and a fuse pair is (point, point).
+ *
+ * Item (item_cam c, keypoint at item_uv with descriptor row item_row, map
+ * point item_pt at X).  The gates run in the reference's order
+ * (SfMHelper.cpp:272-353); the first that fails gives the status, and fields
+ * that were not reached are -1.  Float, round to nearest, no contraction, the
+ * operation order of ba_prune:
+ *   v = extr_c * [X; 1], cz = v2 / v3; cz <= 0 is BA_AS_BEHIND;
+ *   q = K_c * (v0 / v3, v1 / v3, cz) accumulated column by column, px = q0 /
+ *     q2, py = q1 / q2; px < 0 || px >= (float)w || py < 0 || py >= (float)h
+ *     is BA_AS_BOUNDS;
+ *   chi = sqrt(e0 e0 + e1 e1) * invSigma with e = (px, py) - uv and invSigma =
+ *     (float)(1.0 / (double)item_scale); chi > chi2 is BA_AS_CHI2 (a norm, as
+ *     in ba_prune);
+ *   cosine = (w0 n0 + w1 n1) + w2 n2 with w the normalised X - centre_c (as
+ *     the viewing direction above) and n = pt_view_dir; cosine < min_cos is
+ *     BA_AS_ANGLE (a NaN passes, as in the reference);
+ *   world_dist = |X - centre_c|; world_dist > max || world_dist < min of
+ *     pt_dist is BA_AS_DEPTH;
+ *   dist_matched = the descriptor distance (ba_match_descriptors' formulas)
+ *     from desc[item_row] to pt_desc[item_pt].  Not yet observed
+ *     (item_cur_row < 0): dist_matched < max_desc_dist gives BA_AS_ADD, else
+ *     BA_AS_DESC.  Already observed: dist_current is the distance from
+ *     desc[item_cur_row] to pt_desc[item_pt]; dist_matched < dist_current
+ *     gives BA_AS_REPLACE, else BA_AS_WORSE.
+ * Fuse pair (p, q): cosine = (a0 b0 + a1 b1) + a2 b2 of the two view
+ * directions; cosine < fuse_min_cos is BA_FUSE_ANGLE (dist = -1); dist = the
+ * distance between the two pt_desc rows; dist < fuse_max_desc_dist gives
+ * BA_FUSE_OK, else BA_FUSE_DESC.  Which point survives stays with the caller
+ * (getNumObserved).
+ *
+ * Contract and errors as ba_map_points_update; the message names the item.
+ * BA_ERR_INVALID_ARGUMENT: a NULL required array, dim other than 64 / 128,
+ * negative counts, an item_cam, item_pt, item_row, item_cur_row (below -1 or
+ * beyond n_rows) or fuse_pairs entry out of range, a non-zero reserved. */
+enum ba_assoc_status { BA_AS_ADD = 0, BA_AS_REPLACE = 1, BA_AS_BEHIND = 2, BA_AS_BOUNDS = 3, BA_AS_CHI2 = 4,
+                       BA_AS_ANGLE = 5, BA_AS_DEPTH = 6, BA_AS_DESC = 7, BA_AS_WORSE = 8 };
+enum ba_fuse_status  { BA_FUSE_OK = 0, BA_FUSE_ANGLE = 1, BA_FUSE_DESC = 2 };
+
+typedef struct {
+  int32_t dim, n_cams, n_pts, n_rows, n_items, n_fuse;
+  const float *extr, *cam_center, *K;   /* as ba_prune_problem */
+  const int32_t* image_size;            /* [2*n_cams] width, height */
+  const float *pts, *pt_view_dir;       /* [3*n_pts] each */
+  const float *pt_dist;                 /* [2*n_pts] min, max (ba_prune's obs_dist, per point) */
+  const float *pt_desc;                 /* [n_pts*dim] (desc_out of ba_map_points_update) */
+  const float *desc;                    /* [n_rows*dim] keypoint descriptors */
+  const int32_t *item_cam, *item_pt;    /* [n_items] */
+  const float   *item_uv;               /* [2*n_items] */
+  const float   *item_scale;            /* [n_items] pow(1.2, octave); NULL = 1 */
+  const int32_t *item_row;              /* [n_items] the matched keypoint's descriptor row */
+  const int32_t *item_cur_row;          /* [n_items] row of the keypoint through which item_cam already observes
+                                           item_pt, -1 if it does not; NULL = none */
+  const int32_t *fuse_pairs;            /* [2*n_fuse] */
+} ba_assoc_batch;
+
+typedef struct {
+  float chi2, min_cos, max_desc_dist, fuse_min_cos, fuse_max_desc_dist;   /* defaults 5.991f, 0.5f, 0.2f, 0.0f, 0.3f */
+  int32_t reserved;                                                       /* 0 */
+} ba_assoc_options;
+
+typedef struct { int32_t status; float chi, cosine, world_dist, dist_matched, dist_current; } ba_assoc_result;
+typedef struct { int32_t status; float cosine, dist; } ba_fuse_result;
+
+void ba_associate_defaults(ba_assoc_options* opt);
+int ba_associate(ba_ctx* ctx, const ba_assoc_batch* batch, const ba_assoc_options* opt /* NULL = defaults */,
+                 ba_assoc_result* items /* [n_items] */, ba_fuse_result* fuse /* [n_fuse] */);
+
 /* Test / inspection entry point: the state inside ceres::Solve's
  * SchurComplementSolver (Optimizer.cpp:242, DENSE_SCHUR) for one step.
  * Linearises at the current parameters with iteration-0 Jacobi scaling, then
