@@ -257,6 +257,37 @@ class ba_fuse_result(C.Structure):
 FUSE_OK, FUSE_ANGLE, FUSE_DESC = range(3)                                                              # ba_fuse_status
 
 
+class ba_map_table(C.Structure):
+    _fields_ = [
+        ("n_frames", C.c_int32), ("n_pts", C.c_int32), ("n_obs", C.c_int32), ("reserved", C.c_int32),
+        ("frame_id", C.c_void_p), ("frame_is_key", C.c_void_p), ("pt_invalid", C.c_void_p), ("pt_ref_frame", C.c_void_p),
+        ("obs_offset", C.c_void_p), ("obs_frame", C.c_void_p), ("obs_octave", C.c_void_p), ("obs_outlier", C.c_void_p),
+    ]
+
+
+class ba_graph_options(C.Structure):
+    _fields_ = [
+        ("th", C.c_int32), ("n_best", C.c_int32), ("order", C.c_int32), ("build_windows", C.c_int32),
+        ("current_frame_id", C.c_int32), ("debug_tile_frames", C.c_int32), ("debug_chunk_queries", C.c_int32),
+        ("reserved", C.c_int32), ("redundant_fraction", C.c_double),
+    ]
+
+
+class ba_graph_frame(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "degree", "max_weight", "n_map", "n_redundant", "cull", "n_local",
+                                         "n_fixed", "n_win_pts", "n_win_obs")]
+
+
+class ba_graph_lists(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("nbr_frame", "nbr_weight", "win_cam", "win_cam_fixed", "win_pt", "win_obs",
+                                          "win_obs_cam", "win_obs_pt")]
+
+
+GRAPH_OK, GRAPH_FALLBACK, GRAPH_ISOLATED = range(3)                              # ba_graph_status
+GRAPH_WEAKEST_FIRST, GRAPH_STRONGEST_FIRST = range(2)                            # ba_graph_order
+GRAPH_PT_RECENT, GRAPH_PT_MATURE, GRAPH_PT_ERASE, GRAPH_PT_INVALID = range(4)    # ba_graph_pt_status
+
+
 class ba_covariance_request(C.Structure):
     _fields_ = [
         ("n_cam_pairs", C.c_int32), ("n_points", C.c_int32), ("cam_pairs", C.c_void_p), ("cam_cov", C.c_void_p),
@@ -351,6 +382,13 @@ SIGNATURES = [
     ("ba_associate_defaults", None, [C.POINTER(ba_assoc_options)]),
     ("ba_associate", C.c_int, [C.c_void_p, C.POINTER(ba_assoc_batch), C.POINTER(ba_assoc_options), C.c_void_p,
                                C.c_void_p]),
+    ("ba_map_graph_defaults", None, [C.POINTER(ba_graph_options)]),
+    ("ba_map_graph", C.c_int, [C.c_void_p, C.POINTER(ba_map_table), C.c_void_p, C.c_int, C.POINTER(ba_graph_options),
+                               C.c_void_p, C.c_void_p]),
+    ("ba_map_graph_lists", C.c_int, [C.c_void_p, C.POINTER(ba_graph_lists)]),
+    ("ba_map_graph_weights", C.c_int, [C.c_void_p, C.POINTER(ba_map_table), C.c_int, C.POINTER(ba_graph_options),
+                                       C.c_void_p]),
+    ("ba_map_graph_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
     ("ba_covariance_ex", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request_ex)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

@@ -494,6 +494,45 @@ struct AssocArgs {
 };
 void launch_associate(const AssocArgs& A, hipStream_t s);
 
+// covisibility lists, culling votes and local-BA windows of a chunk of query frames (ba_map_graph.hip)
+struct MapGraphArgs {
+  int n_frames, n_pts, n_obs;
+  int th, n_best, order, build_windows, tile;
+  double fraction;
+  // the table and its frame-sorted view (MapGraphPlan); the optional arrays may be null
+  const int* frame_id;
+  const uint8_t* is_key;
+  const uint8_t* pt_invalid;
+  const int* obs_offset;
+  const int* obs_frame;
+  const int* obs_octave;
+  const uint8_t* obs_outlier;
+  const int* obs_pt;
+  const int* perm;
+  const int* frame_off;
+  // the chunk
+  const int* query;                // [n_chunk]
+  int n_chunk;
+  ba_graph_frame* rec;             // [n_chunk]
+  // scratch, one slice per query of the chunk
+  int* W;                          // [n_chunk][n_frames]
+  int *lst_f, *lst_w;              // [n_chunk][n_frames] the list in order
+  int* best;                       // [n_chunk][BA_WINDOW_MAX_CAMS] the best frames in order
+  unsigned *locbits, *fixbits;     // [n_chunk][words(n_frames)] (zero before the count launches)
+  int* fixpre;                     // [n_chunk][words(n_frames)] fixed frames before each word
+  unsigned* ptbits;                // [n_chunk][words(n_pts)] (zero before the count launches)
+  // the fill: per query the first element of its lists (neighbours, cameras, points, observations)
+  const long long* off;            // [n_chunk][4]
+  int *nbr_frame, *nbr_weight, *win_cam;
+  uint8_t* win_cam_fixed;
+  int *win_pt, *win_obs, *win_obs_cam, *win_obs_pt;
+};
+void launch_map_graph_weights(const MapGraphArgs& A, hipStream_t s);   // W rows only
+void launch_map_graph_count(const MapGraphArgs& A, hipStream_t s);     // W, lists, votes, window counts: the records
+void launch_map_graph_fill(const MapGraphArgs& A, hipStream_t s);      // the lists at A.off
+void launch_map_graph_status(const MapGraphArgs& A, const int* pt_ref_frame, int current_frame_id, uint8_t* pt_status,
+                             hipStream_t s);
+
 int grid_for(int n);
 int pt_group_grid(int np);   // grid of the kPtLanes-lanes-per-point kernels
 

@@ -68,6 +68,19 @@ struct StagingArena {
   void reserve(ba_ctx* ctx, size_t bytes, const std::string& fn);
 };
 
+// The variable-length lists of the last ba_map_graph, on the device: the eight
+// arrays of ba_graph_lists in its order, grown chunk by chunk.  len: elements
+// of the neighbour, camera, point and observation lists.
+struct GraphLists {
+  static constexpr int kArrays = 8;
+  static constexpr size_t elem[kArrays] = {4, 4, 4, 1, 4, 4, 4, 4};
+  static constexpr int kind[kArrays] = {0, 0, 1, 1, 2, 3, 3, 3};
+  char* buf[kArrays] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t cap[kArrays] = {0, 0, 0, 0, 0, 0, 0, 0};   // elements
+  size_t len[4] = {0, 0, 0, 0};
+  bool valid = false;
+};
+
 // hipFree at scope exit (buffers that live for one call)
 struct DevFree { void* p; ~DevFree() { (void)hipFree(p); } };
 
@@ -113,7 +126,8 @@ struct ba_ctx {
   // ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors and
   // ba_map_points_update / ba_associate (one each: a call of one never makes
   // another reallocate)
-  StagingArena pose, win, tri, pnp, tv, match, mp;
+  StagingArena pose, win, tri, pnp, tv, match, mp, mg;
+  GraphLists graph;                    // the lists of the last ba_map_graph (device)
   // ba_solve_window_batch: the last call's logs and times
   std::vector<ba_iteration> win_log;   // [n_problems][win_log_cap]
   std::vector<int> win_log_n;
@@ -124,6 +138,7 @@ struct ba_ctx {
   std::vector<double> tv_ms;           // ba_two_view_times of the last call
   std::vector<double> match_ms;        // ba_match_times of the last call
   std::vector<double> mp_ms;           // ba_map_points_times of the last call
+  std::vector<double> mg_ms;           // ba_map_graph_times of the last call
   hipEvent_t match_ev[3] = {nullptr, nullptr, nullptr};   // phase stamps of ba_match_descriptors (created by its first call)
 
   // host copies of the sorted structure, kept for the lazily built
@@ -2083,7 +2098,8 @@ int ba_destroy(ba_ctx* ctx) {
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
-  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv, &ctx->match, &ctx->mp}) (void)hipFree(a->dev);
+  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv, &ctx->match, &ctx->mp, &ctx->mg}) (void)hipFree(a->dev);
+  for (char* b : ctx->graph.buf) (void)hipFree(b);
   for (hipEvent_t e : ctx->match_ev) if (e) (void)hipEventDestroy(e);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -3153,6 +3169,210 @@ int ba_associate(ba_ctx* ctx, const ba_assoc_batch* b, const ba_assoc_options* o
     if (ni) std::memcpy(items, h.data() + P.items, sizeof(ba_assoc_result) * ni);
     if (nf) std::memcpy(fuse, h.data() + P.fused, sizeof(ba_fuse_result) * nf);
   });
+}
+
+// ---------------------------------------------------------------------------
+// ba_map_graph / ba_map_graph_lists / ba_map_graph_weights: host side.
+// Validation, the frame-sorted view and the chunk size are plain C++
+// (check_map_table, map_graph_plan, map_graph_chunk: host/ba_batch_pack.hpp).
+// The table goes up from the caller's arrays once; the queries are served in
+// chunks under a fixed scratch budget: count launches, the chunk's records to
+// the host, a scan there, then the fill launches into the context's list
+// buffers.  The context's current problem is not touched.
+// ---------------------------------------------------------------------------
+void ba_map_graph_defaults(ba_graph_options* opt) {
+  if (opt) map_graph_defaults(*opt);
+}
+
+namespace {
+
+struct MapGraphLayout {
+  SectionLayout L{256};
+  size_t frame_id = 0, is_key = 0, pt_invalid = 0, pt_ref = 0, off = 0, frame = 0, octave = 0, outlier = 0, obs_pt = 0,
+         perm = 0, frame_off = 0, query = 0;
+  size_t rec = 0, status = 0;
+  size_t W = 0, lst_f = 0, lst_w = 0, best = 0, loc = 0, fix = 0, pre = 0, ptb = 0, offs = 0;
+};
+
+// Uploads the table, its frame-sorted view and the queries into ctx->mg and
+// returns the kernel arguments with the scratch of `chunk` queries.
+MapGraphArgs map_graph_stage(ba_ctx* ctx, const ba_map_table* t, const MapGraphPlan& M, const int32_t* query, int n_query,
+                             const ba_graph_options& p, int chunk, bool want_status, MapGraphLayout& P,
+                             const std::string& fn) {
+  const size_t nf = (size_t)t->n_frames, np = (size_t)t->n_pts, no = (size_t)t->n_obs, nq = (size_t)n_query,
+               fw = map_graph_words(t->n_frames), pw = p.build_windows ? map_graph_words(t->n_pts) : 0, nc = (size_t)chunk;
+  SectionLayout& L = P.L;
+  P.frame_id = L.add(4 * nf); P.is_key = L.add(t->frame_is_key ? nf : 0); P.pt_invalid = L.add(t->pt_invalid ? np : 0);
+  P.pt_ref = L.add(want_status ? 4 * np : 0); P.off = L.add(4 * (np + 1)); P.frame = L.add(4 * no);
+  P.octave = L.add(t->obs_octave ? 4 * no : 0); P.outlier = L.add(t->obs_outlier ? no : 0); P.obs_pt = L.add(4 * no);
+  P.perm = L.add(4 * no); P.frame_off = L.add(4 * (nf + 1)); P.query = L.add(4 * nq);
+  L.end_inputs();
+  P.rec = L.add(sizeof(ba_graph_frame) * nq); P.status = L.add(want_status ? np : 0);
+  L.end_outputs();
+  P.W = L.add(4 * nc * nf); P.lst_f = L.add(4 * nc * nf); P.lst_w = L.add(4 * nc * nf);
+  P.best = L.add(4 * nc * BA_WINDOW_MAX_CAMS); P.loc = L.add(4 * nc * fw); P.fix = L.add(4 * nc * fw);
+  P.pre = L.add(4 * nc * fw); P.ptb = L.add(4 * nc * pw); P.offs = L.add(sizeof(long long) * 4 * nc);
+  HIP_OK(hipSetDevice(ctx->device));
+  ctx->mg.reserve(ctx, L.total, fn);
+  char* d = ctx->mg.dev;
+  auto up = [&](size_t off, const void* src, size_t nb) {
+    if (src && nb) HIP_OK(hipMemcpyAsync(d + off, src, nb, hipMemcpyHostToDevice, ctx->stream));
+  };
+  up(P.frame_id, t->frame_id, 4 * nf); up(P.is_key, t->frame_is_key, nf); up(P.pt_invalid, t->pt_invalid, np);
+  if (want_status) up(P.pt_ref, t->pt_ref_frame, 4 * np);
+  up(P.off, t->obs_offset, 4 * (np + 1)); up(P.frame, t->obs_frame, 4 * no); up(P.octave, t->obs_octave, 4 * no);
+  up(P.outlier, t->obs_outlier, no); up(P.obs_pt, M.obs_pt.data(), 4 * no); up(P.perm, M.perm.data(), 4 * no);
+  up(P.frame_off, M.frame_off.data(), 4 * (nf + 1)); up(P.query, query, 4 * nq);
+  MapGraphArgs A{};
+  A.n_frames = t->n_frames; A.n_pts = t->n_pts; A.n_obs = t->n_obs;
+  A.th = p.th; A.n_best = p.n_best; A.order = p.order; A.build_windows = p.build_windows ? 1 : 0;
+  A.tile = map_graph_tile(p, t->n_frames); A.fraction = p.redundant_fraction;
+  A.frame_id = at<const int>(d, P.frame_id);
+  A.is_key = t->frame_is_key ? at<const uint8_t>(d, P.is_key) : nullptr;
+  A.pt_invalid = t->pt_invalid ? at<const uint8_t>(d, P.pt_invalid) : nullptr;
+  A.obs_offset = at<const int>(d, P.off); A.obs_frame = at<const int>(d, P.frame);
+  A.obs_octave = t->obs_octave ? at<const int>(d, P.octave) : nullptr;
+  A.obs_outlier = t->obs_outlier ? at<const uint8_t>(d, P.outlier) : nullptr;
+  A.obs_pt = at<const int>(d, P.obs_pt); A.perm = at<const int>(d, P.perm); A.frame_off = at<const int>(d, P.frame_off);
+  A.W = at<int>(d, P.W); A.lst_f = at<int>(d, P.lst_f); A.lst_w = at<int>(d, P.lst_w); A.best = at<int>(d, P.best);
+  A.locbits = at<unsigned>(d, P.loc); A.fixbits = at<unsigned>(d, P.fix); A.fixpre = at<int>(d, P.pre);
+  A.ptbits = at<unsigned>(d, P.ptb); A.off = at<const long long>(d, P.offs);
+  return A;
+}
+
+// Room for `need` elements in list array a, keeping the first `keep`
+void graph_lists_reserve(ba_ctx* ctx, int a, size_t need, size_t keep, const std::string& fn) {
+  GraphLists& G = ctx->graph;
+  if (need <= G.cap[a]) return;
+  const size_t cap = std::max(need, 2 * G.cap[a]), es = GraphLists::elem[a];
+  char* nb = nullptr;
+  const hipError_t e = hipMalloc(&nb, cap * es);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    throw BaError{e == hipErrorOutOfMemory ? BA_ERR_OUT_OF_MEMORY : BA_ERR_DEVICE,
+                  fn + "lists of " + std::to_string(cap * es) + " bytes: " + hipGetErrorString(e)};
+  }
+  if (G.buf[a]) {
+    if (keep) HIP_OK(hipMemcpyAsync(nb, G.buf[a], keep * es, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    (void)hipFree(G.buf[a]);
+  }
+  G.buf[a] = nb; G.cap[a] = cap;
+}
+
+}  // namespace
+
+int ba_map_graph(ba_ctx* ctx, const ba_map_table* t, const int32_t* query, int n_query, const ba_graph_options* opt,
+                 ba_graph_frame* out, uint8_t* pt_status) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_map_graph: ";
+    const bool want_status = pt_status != nullptr;
+    const ba_graph_options p = check_map_table(fn.c_str(), t, query, n_query, opt, want_status);
+    if (n_query > 0 && !out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const double t0 = now_s();
+    GraphLists& G = ctx->graph;
+    G.valid = false;
+    for (size_t& l : G.len) l = 0;
+    const MapGraphPlan M = map_graph_plan(t);
+    const int chunk = map_graph_chunk(p, t, n_query);
+    MapGraphLayout P;
+    MapGraphArgs A = map_graph_stage(ctx, t, M, query, n_query, p, chunk, want_status, P, fn);
+    char* d = ctx->mg.dev;
+    const double t_prep = now_s() - t0;
+    double kernel_ms = 0.0;
+    auto timed = [&](auto&& launches) {
+      HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
+      launches();
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
+    };
+    auto add_time = [&] {
+      float ms = 0.0f;
+      HIP_OK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      kernel_ms += (double)ms;
+    };
+    std::vector<long long> offs;
+    for (int c0 = 0; c0 < n_query; c0 += chunk) {
+      const int n = std::min(chunk, n_query - c0);
+      A.query = at<const int>(d, P.query) + c0; A.rec = at<ba_graph_frame>(d, P.rec) + c0; A.n_chunk = n;
+      if (p.build_windows && P.offs > P.loc) HIP_OK(hipMemsetAsync(d + P.loc, 0, P.offs - P.loc, ctx->stream));
+      timed([&] { launch_map_graph_count(A, ctx->stream); });
+      HIP_OK(hipMemcpyAsync(out + c0, A.rec, sizeof(ba_graph_frame) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_OK(hipStreamSynchronize(ctx->stream));
+      add_time();
+      offs.resize(4 * (size_t)n);
+      size_t len[4] = {G.len[0], G.len[1], G.len[2], G.len[3]};
+      for (int i = 0; i < n; ++i) {
+        const ba_graph_frame& r = out[c0 + i];
+        for (int k = 0; k < 4; ++k) offs[4 * (size_t)i + k] = (long long)len[k];
+        len[0] += (size_t)r.degree; len[1] += (size_t)(r.n_local + r.n_fixed); len[2] += (size_t)r.n_win_pts;
+        len[3] += (size_t)r.n_win_obs;
+      }
+      for (int a = 0; a < GraphLists::kArrays; ++a)
+        graph_lists_reserve(ctx, a, len[GraphLists::kind[a]], G.len[GraphLists::kind[a]], fn);
+      for (int k = 0; k < 4; ++k) G.len[k] = len[k];
+      HIP_OK(hipMemcpyAsync(d + P.offs, offs.data(), sizeof(long long) * offs.size(), hipMemcpyHostToDevice, ctx->stream));
+      A.nbr_frame = at<int>(G.buf[0], 0); A.nbr_weight = at<int>(G.buf[1], 0); A.win_cam = at<int>(G.buf[2], 0);
+      A.win_cam_fixed = at<uint8_t>(G.buf[3], 0); A.win_pt = at<int>(G.buf[4], 0); A.win_obs = at<int>(G.buf[5], 0);
+      A.win_obs_cam = at<int>(G.buf[6], 0); A.win_obs_pt = at<int>(G.buf[7], 0);
+      timed([&] { launch_map_graph_fill(A, ctx->stream); });
+      HIP_OK(hipStreamSynchronize(ctx->stream));
+      add_time();
+    }
+    if (want_status && t->n_pts > 0) {
+      timed([&] {
+        launch_map_graph_status(A, at<const int>(d, P.pt_ref), p.current_frame_id, at<uint8_t>(d, P.status), ctx->stream);
+      });
+      HIP_OK(hipMemcpyAsync(pt_status, d + P.status, (size_t)t->n_pts, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_OK(hipStreamSynchronize(ctx->stream));
+      add_time();
+    }
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    G.valid = true;
+    ctx->mg_ms = {1e3 * t_prep, kernel_ms, 1e3 * (now_s() - t0)};
+  });
+}
+
+int ba_map_graph_lists(ba_ctx* ctx, const ba_graph_lists* out) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_map_graph_lists: ";
+    if (!out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output"};
+    const GraphLists& G = ctx->graph;
+    if (!G.valid) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "no ba_map_graph result on this context"};
+    void* dst[GraphLists::kArrays] = {out->nbr_frame, out->nbr_weight, out->win_cam, out->win_cam_fixed,
+                                      out->win_pt, out->win_obs, out->win_obs_cam, out->win_obs_pt};
+    HIP_OK(hipSetDevice(ctx->device));
+    for (int a = 0; a < GraphLists::kArrays; ++a) {
+      const size_t nb = G.len[GraphLists::kind[a]] * GraphLists::elem[a];
+      if (dst[a] && nb) HIP_OK(hipMemcpyAsync(dst[a], G.buf[a], nb, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+  });
+}
+
+int ba_map_graph_weights(ba_ctx* ctx, const ba_map_table* t, int frame, const ba_graph_options* opt, int32_t* W) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_map_graph_weights: ";
+    const int32_t q = frame;
+    ba_graph_options p = check_map_table(fn.c_str(), t, &q, 1, opt, false);
+    if (!W) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    p.build_windows = 0;
+    const MapGraphPlan M = map_graph_plan(t);
+    MapGraphLayout P;
+    MapGraphArgs A = map_graph_stage(ctx, t, M, &q, 1, p, 1, false, P, fn);
+    A.query = at<const int>(ctx->mg.dev, P.query); A.n_chunk = 1;
+    launch_map_graph_weights(A, ctx->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(W, A.W, sizeof(int32_t) * (size_t)t->n_frames, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+  });
+}
+
+int ba_map_graph_times(ba_ctx* ctx, double* ms, int n) {
+  return ctx ? copy_times(ctx->mg_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
 }
 
 int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double* Hcc, double* gc, double* S,

@@ -1,7 +1,8 @@
 // ba_batch_pack.hpp — host-only packing shared by the batch entry points of
 // ba_solver.hip: the error type, the section layout of a staging buffer, the
 // CSR-offset validation, the summary record, the validation and layout of
-// ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors, ba_map_points_update and ba_associate, and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
+// ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors, ba_map_points_update, ba_associate and
+// ba_map_graph (with its plain restatement), and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
 // plain C++17 without a HIP header and runs under ASan + UBSan
 // (tests/cpp/batch_pack.cpp, `make -C tests/cpp sanitize`).
 #pragma once
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "../../include/ba_hip.h"
+#include "../csrc/ba_map_graph.h"
 
 namespace bahip {
 
@@ -483,6 +485,206 @@ inline AssocLayout assoc_layout(const ba_assoc_batch* b) {
   P.items = L.add(sizeof(ba_assoc_result) * ni); P.fused = L.add(sizeof(ba_fuse_result) * nf);
   L.end_outputs();
   return P;
+}
+
+// ---------------------------------------------------------------------------
+// ba_map_graph / ba_map_graph_weights
+// ---------------------------------------------------------------------------
+inline void map_graph_defaults(ba_graph_options& o) {
+  o.th = 10; o.n_best = 10; o.order = BA_GRAPH_WEAKEST_FIRST; o.build_windows = 1; o.current_frame_id = 0;
+  o.debug_tile_frames = 0; o.debug_chunk_queries = 0; o.reserved = 0; o.redundant_fraction = 0.95;
+}
+
+// Everything the kernels index with or branch on, checked on the host; the
+// options are returned with the defaults applied.
+inline ba_graph_options check_map_table(const char* fn, const ba_map_table* t, const int32_t* query, int n_query,
+                                        const ba_graph_options* opt, bool want_status) {
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what}; };
+  if (!t || t->n_frames < 0 || t->n_pts < 0 || t->n_obs < 0 || n_query < 0) throw invalid("bad table");
+  if (t->reserved != 0) throw invalid("reserved must be 0");
+  ba_graph_options p;
+  if (opt) p = *opt; else map_graph_defaults(p);
+  if (p.n_best < 0 || p.n_best > BA_WINDOW_MAX_CAMS - 1)
+    throw invalid("n_best " + std::to_string(p.n_best) + " outside 0 .. " + std::to_string(BA_WINDOW_MAX_CAMS - 1));
+  if (p.order != BA_GRAPH_WEAKEST_FIRST && p.order != BA_GRAPH_STRONGEST_FIRST)
+    throw invalid("unknown order " + std::to_string(p.order));
+  if (p.th < 0) throw invalid("th " + std::to_string(p.th) + " is negative");
+  if (!(p.redundant_fraction >= -std::numeric_limits<double>::max() && p.redundant_fraction <= std::numeric_limits<double>::max()))
+    throw invalid("redundant_fraction must be finite");
+  if (p.debug_tile_frames < 0 || p.debug_chunk_queries < 0) throw invalid("a debug field is negative");
+  if (p.reserved != 0) throw invalid("reserved must be 0");
+  if (want_status && t->n_pts > 0 && !t->pt_ref_frame) throw invalid("pt_status needs pt_ref_frame");
+  if (t->n_frames > 0 && !t->frame_id) throw invalid("null array frame_id");
+  if (!t->obs_offset) throw invalid("null array obs_offset");
+  check_offsets(fn, "obs_offset", t->obs_offset, t->n_pts, "point");
+  if (t->obs_offset[t->n_pts] != t->n_obs)
+    throw invalid("obs_offset[n_pts] is " + std::to_string(t->obs_offset[t->n_pts]) + ", not n_obs " + std::to_string(t->n_obs));
+  if (t->n_obs > 0 && !t->obs_frame) throw invalid("null array obs_frame");
+  for (int o = 0; o < t->n_obs; ++o)
+    if (t->obs_frame[o] < 0 || t->obs_frame[o] >= t->n_frames) throw invalid("obs_frame[" + std::to_string(o) + "] out of range");
+  if (t->pt_ref_frame)
+    for (int q = 0; q < t->n_pts; ++q)
+      if (t->pt_ref_frame[q] < 0 || t->pt_ref_frame[q] >= t->n_frames)
+        throw invalid("pt_ref_frame[" + std::to_string(q) + "] out of range");
+  if (n_query > 0 && !query) throw invalid("null array query");
+  for (int i = 0; i < n_query; ++i)
+    if (query[i] < 0 || query[i] >= t->n_frames) throw invalid("query[" + std::to_string(i) + "] out of range");
+  return p;
+}
+
+// The frame-sorted view of the table: frame f owns perm[frame_off[f] ..
+// frame_off[f+1]), its observations in ascending o (count, scan, stable
+// scatter), and obs_pt[o] is the point of observation o.
+struct MapGraphPlan {
+  std::vector<int32_t> frame_off, perm, obs_pt;
+};
+inline MapGraphPlan map_graph_plan(const ba_map_table* t) {
+  MapGraphPlan M;
+  const size_t nf = (size_t)t->n_frames, no = (size_t)t->n_obs;
+  M.frame_off.assign(nf + 1, 0); M.perm.resize(no); M.obs_pt.resize(no);
+  for (size_t o = 0; o < no; ++o) ++M.frame_off[(size_t)t->obs_frame[o] + 1];
+  for (size_t f = 0; f < nf; ++f) M.frame_off[f + 1] += M.frame_off[f];
+  std::vector<int32_t> next(M.frame_off.begin(), M.frame_off.end() - 1);
+  for (int p = 0; p < t->n_pts; ++p)
+    for (int o = t->obs_offset[p]; o < t->obs_offset[p + 1]; ++o) {
+      M.obs_pt[(size_t)o] = p;
+      M.perm[(size_t)next[(size_t)t->obs_frame[o]]++] = o;
+    }
+  return M;
+}
+
+inline int map_graph_tile(const ba_graph_options& p, int n_frames) {
+  const int T = p.debug_tile_frames > 0 ? p.debug_tile_frames : kMgTileMax;
+  return std::max(1, std::min(std::min(T, kMgTileMax), std::max(n_frames, 1)));
+}
+inline size_t map_graph_words(int n) { return ((size_t)n + 31) / 32; }
+// Device scratch of one query: the W row, the sorted list (frame, weight), the
+// best frames, the local / fixed frame bitmaps with the fixed prefix counts,
+// and the point bitmap
+inline size_t map_graph_query_bytes(const ba_map_table* t, bool windows) {
+  const size_t nf = (size_t)t->n_frames;
+  return 4 * (3 * nf + BA_WINDOW_MAX_CAMS + 3 * map_graph_words(t->n_frames) + (windows ? map_graph_words(t->n_pts) : 0)) + 64;
+}
+inline int map_graph_chunk(const ba_graph_options& p, const ba_map_table* t, int n_query) {
+  if (p.debug_chunk_queries > 0) return std::min(p.debug_chunk_queries, std::max(n_query, 1));
+  const size_t fit = kMgChunkBudget / map_graph_query_bytes(t, p.build_windows != 0);
+  return (int)std::max<size_t>(1, std::min<size_t>(fit, (size_t)std::max(n_query, 1)));
+}
+
+// The plain restatement of ba_map_graph, query by query, on one thread: what
+// the kernels of ba_map_graph.hip compute (tests/cpp/map_graph_host.cpp runs it
+// under ASan + UBSan; tools/map_graph_bench.py times it).
+struct MapGraphHost {
+  std::vector<ba_graph_frame> rec;
+  std::vector<int32_t> nbr_frame, nbr_weight, win_cam, win_pt, win_obs, win_obs_cam, win_obs_pt;
+  std::vector<uint8_t> win_cam_fixed, pt_status;
+};
+inline void map_graph_host_weights(const ba_map_table* t, const MapGraphPlan& M, int q, std::vector<int32_t>& W) {
+  W.assign((size_t)t->n_frames, 0);
+  for (int i = M.frame_off[(size_t)q]; i < M.frame_off[(size_t)q + 1]; ++i) {
+    const int o = M.perm[(size_t)i];
+    if (t->obs_outlier && t->obs_outlier[o]) continue;
+    const int p = M.obs_pt[(size_t)o];
+    for (int k = t->obs_offset[p]; k < t->obs_offset[p + 1]; ++k)
+      if (t->obs_frame[k] != q) ++W[(size_t)t->obs_frame[k]];
+  }
+}
+inline MapGraphHost map_graph_host(const ba_map_table* t, const MapGraphPlan& M, const int32_t* query, int n_query,
+                                   const ba_graph_options& p, bool want_status) {
+  MapGraphHost R;
+  const int nf = t->n_frames;
+  auto is_key = [&](int g) { return !t->frame_is_key || t->frame_is_key[g] != 0; };
+  auto invalid = [&](int pt) { return t->pt_invalid && t->pt_invalid[pt] != 0; };
+  auto outlier = [&](int o) { return t->obs_outlier && t->obs_outlier[o] != 0; };
+  auto octave = [&](int o) { return t->obs_octave ? t->obs_octave[o] : 0; };
+  std::vector<int32_t> W;
+  std::vector<uint8_t> local((size_t)nf), fixed((size_t)nf), pt_local((size_t)t->n_pts);
+  std::vector<int32_t> cam_of((size_t)nf), pt_rank((size_t)t->n_pts);
+  for (int qi = 0; qi < n_query; ++qi) {
+    const int q = query[qi];
+    ba_graph_frame r{};
+    map_graph_host_weights(t, M, q, W);
+    std::vector<std::pair<uint64_t, int32_t>> list;
+    uint64_t fb = 0;
+    for (int g = 0; g < nf; ++g) {
+      r.max_weight = std::max(r.max_weight, W[(size_t)g]);
+      if (W[(size_t)g] > 0) fb = std::max(fb, mg_fallback_key(W[(size_t)g], g));
+      if (W[(size_t)g] > p.th && is_key(g)) list.push_back({mg_list_key(W[(size_t)g], g), g});
+    }
+    r.status = BA_GRAPH_OK;
+    if (list.empty()) {
+      if (r.max_weight > 0) {
+        const int32_t g = (int32_t)(0xffffffffu - (uint32_t)fb);
+        list.push_back({mg_list_key(W[(size_t)g], g), g});
+        r.status = BA_GRAPH_FALLBACK;
+      } else {
+        r.status = BA_GRAPH_ISOLATED;
+      }
+    }
+    std::sort(list.begin(), list.end());
+    r.degree = (int32_t)list.size();
+    for (auto& e : list) { R.nbr_frame.push_back(e.second); R.nbr_weight.push_back(W[(size_t)e.second]); }
+    std::vector<int32_t> best;
+    for (auto& e : list) best.push_back(e.second);
+    if (p.order == BA_GRAPH_STRONGEST_FIRST)
+      std::sort(best.begin(), best.end(), [&](int32_t a, int32_t b) { return mg_stronger(W[(size_t)a], a, W[(size_t)b], b); });
+    best.resize((size_t)std::min<int>(p.n_best, r.degree));
+    // the vote
+    for (int i = M.frame_off[(size_t)q]; i < M.frame_off[(size_t)q + 1]; ++i) {
+      const int o = M.perm[(size_t)i], pt = M.obs_pt[(size_t)o];
+      if (invalid(pt)) continue;
+      ++r.n_map;
+      if (t->obs_offset[pt + 1] - t->obs_offset[pt] <= kMgMinTrack) continue;
+      int views = 0;
+      for (int k = t->obs_offset[pt]; k < t->obs_offset[pt + 1]; ++k)
+        views += t->obs_frame[k] != q && mg_view_counts(octave(k), octave(o)) ? 1 : 0;
+      r.n_redundant += views >= kMgMinViews ? 1 : 0;
+    }
+    r.cull = mg_cull(t->frame_id[q], r.n_map, r.n_redundant, p.redundant_fraction);
+    if (p.build_windows) {
+      r.n_local = (int32_t)best.size() + 1;
+      std::vector<int32_t> cams(best);
+      cams.push_back(q);
+      std::fill(local.begin(), local.end(), 0); std::fill(fixed.begin(), fixed.end(), 0);
+      std::fill(pt_local.begin(), pt_local.end(), 0);
+      for (size_t c = 0; c < cams.size(); ++c) { local[(size_t)cams[c]] = 1; cam_of[(size_t)cams[c]] = (int32_t)c; }
+      for (int32_t f : cams)
+        for (int i = M.frame_off[(size_t)f]; i < M.frame_off[(size_t)f + 1]; ++i) {
+          const int o = M.perm[(size_t)i];
+          if (!outlier(o) && !invalid(M.obs_pt[(size_t)o])) pt_local[(size_t)M.obs_pt[(size_t)o]] = 1;
+        }
+      for (int pt = 0; pt < t->n_pts; ++pt) {
+        if (!pt_local[(size_t)pt]) continue;
+        pt_rank[(size_t)pt] = r.n_win_pts++;
+        R.win_pt.push_back(pt);
+        for (int k = t->obs_offset[pt]; k < t->obs_offset[pt + 1]; ++k)
+          if (!outlier(k) && !local[(size_t)t->obs_frame[k]] && is_key(t->obs_frame[k])) fixed[(size_t)t->obs_frame[k]] = 1;
+      }
+      for (int g = 0; g < nf; ++g)
+        if (fixed[(size_t)g]) { cam_of[(size_t)g] = r.n_local + r.n_fixed++; cams.push_back(g); }
+      for (size_t c = 0; c < cams.size(); ++c) {
+        R.win_cam.push_back(cams[c]);
+        R.win_cam_fixed.push_back((int)c >= r.n_local || t->frame_id[cams[c]] == 0 ? 1 : 0);
+      }
+      for (int pt = 0; pt < t->n_pts; ++pt) {
+        if (!pt_local[(size_t)pt]) continue;
+        for (int k = t->obs_offset[pt]; k < t->obs_offset[pt + 1]; ++k) {
+          const int g = t->obs_frame[k];
+          if (outlier(k) || !(local[(size_t)g] || fixed[(size_t)g])) continue;
+          ++r.n_win_obs;
+          R.win_obs.push_back(k); R.win_obs_cam.push_back(cam_of[(size_t)g]); R.win_obs_pt.push_back(pt_rank[(size_t)pt]);
+        }
+      }
+    }
+    R.rec.push_back(r);
+  }
+  if (want_status) {
+    R.pt_status.resize((size_t)t->n_pts);
+    for (int pt = 0; pt < t->n_pts; ++pt)
+      R.pt_status[(size_t)pt] = mg_point_status(invalid(pt), (int64_t)p.current_frame_id - t->frame_id[t->pt_ref_frame[pt]],
+                                                t->obs_offset[pt + 1] - t->obs_offset[pt]);
+  }
+  return R;
 }
 
 // One problem of ba_solve_window_batch as the kernel (ba_window.hip) reads it

@@ -599,3 +599,103 @@ def pack_assoc_batch(extr, cam_center, K, image_size, pts, pt_view_dir, pt_dist,
                       item_scale=None if item_scale is None else _f32(item_scale, (-1,)), item_row=_i32(item_row),
                       item_cur_row=None if item_cur_row is None else _i32(item_cur_row),
                       fuse_pairs=_i32(fuse_pairs, (-1, 2)))
+
+
+# one record of Solver.map_graph (ba_graph_frame, include/ba_hip.h)
+GRAPH_FRAME_DTYPE = np.dtype([(n, np.int32) for n in ("status", "degree", "max_weight", "n_map", "n_redundant", "cull",
+                                                       "n_local", "n_fixed", "n_win_pts", "n_win_obs")])
+
+
+@dataclass
+class MapTable:
+    """The arrays of the C-ABI's ba_map_table: a point-sorted observation table.
+    Point p owns observations [obs_offset[p], obs_offset[p+1]), its track."""
+    frame_id: np.ndarray               # (F,) int32: Frame::getID()
+    obs_offset: np.ndarray             # (P + 1,) int32
+    obs_frame: np.ndarray              # (O,) int32
+    frame_is_key: np.ndarray | None = None   # (F,) uint8; None: all 1
+    pt_invalid: np.ndarray | None = None     # (P,) uint8; None: all 0
+    pt_ref_frame: np.ndarray | None = None   # (P,) int32; needed for the point status only
+    obs_octave: np.ndarray | None = None     # (O,) int32; None: all 0
+    obs_outlier: np.ndarray | None = None    # (O,) uint8; None: all 0
+    order: np.ndarray | None = None          # (O,) the problem's observation index of each table observation
+
+    @property
+    def n_frames(self) -> int:
+        return int(self.frame_id.shape[0])
+
+    @property
+    def n_pts(self) -> int:
+        return int(self.obs_offset.shape[0]) - 1
+
+    @property
+    def n_obs(self) -> int:
+        return int(self.obs_frame.shape[0])
+
+    def normalized(self) -> "MapTable":
+        u8 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+        i32 = lambda a: None if a is None else _i32(a)
+        return MapTable(frame_id=_i32(self.frame_id), obs_offset=_i32(self.obs_offset), obs_frame=_i32(self.obs_frame),
+                        frame_is_key=u8(self.frame_is_key), pt_invalid=u8(self.pt_invalid),
+                        pt_ref_frame=i32(self.pt_ref_frame), obs_octave=i32(self.obs_octave),
+                        obs_outlier=u8(self.obs_outlier), order=self.order)
+
+
+def map_table_from_problem(problem: Problem, frame_id=None, octave=None, outlier=None, frame_is_key=None,
+                           pt_invalid=None, pt_ref_frame=None) -> MapTable:
+    """The observation table of a Problem for Solver.map_graph: cameras are
+    frames (frame_id defaults to the camera index).  octave and outlier are per
+    observation in the problem's order.  The observations are put in point
+    order (a stable sort; a Problem from make_synthetic already is) and
+    `order` keeps the problem's index of each."""
+    obs_pt = np.asarray(problem.obs_pt, np.int64)
+    order = np.argsort(obs_pt, kind="stable")
+    off = np.zeros(problem.n_pts + 1, np.int64)
+    np.cumsum(np.bincount(obs_pt, minlength=problem.n_pts), out=off[1:])
+    take = lambda a, dt: None if a is None else np.ascontiguousarray(np.asarray(a, dt).reshape(-1)[order])
+    return MapTable(frame_id=_i32(np.arange(problem.n_cams) if frame_id is None else frame_id),
+                    obs_offset=off.astype(np.int32), obs_frame=take(problem.obs_cam, np.int32),
+                    frame_is_key=frame_is_key, pt_invalid=pt_invalid, pt_ref_frame=pt_ref_frame,
+                    obs_octave=take(octave, np.int32), obs_outlier=take(outlier, np.uint8), order=order).normalized()
+
+
+@dataclass
+class MapGraphResult:
+    """What Solver.map_graph returns: the records (GRAPH_FRAME_DTYPE, one per
+    query) and the variable-length lists split per query."""
+    query: np.ndarray
+    records: np.ndarray
+    nbr_frame: list
+    nbr_weight: list
+    win_cam: list
+    win_cam_fixed: list
+    win_pt: list
+    win_obs: list
+    win_obs_cam: list
+    win_obs_pt: list
+    pt_status: np.ndarray | None = None
+    table: MapTable | None = field(default=None, repr=False)
+
+
+def windows_from_graph(problem: Problem, result: MapGraphResult) -> list[Problem]:
+    """The local-BA window of every query of `result` (Solver.map_graph on
+    map_table_from_problem(problem) with build_windows) as a Problem that
+    Solver.solve_window_batch accepts: the window's cameras, K, points and the
+    uv of its observations, cam_fixed from win_cam_fixed, and for a fixed
+    camera the float extrinsic and the re-derived pose as fix_camera forms
+    them."""
+    order = None if result.table is None else result.table.order
+    out = []
+    for i in range(len(result.win_cam)):
+        cam, pt, obs = result.win_cam[i], result.win_pt[i], result.win_obs[i]
+        src = obs if order is None else order[obs]
+        w = Problem(cams=problem.cams[cam].copy(), K=problem.K[cam].copy(), pts=problem.pts[pt].copy(),
+                    obs_cam=result.win_obs_cam[i].astype(np.int32), obs_pt=result.win_obs_pt[i].astype(np.int32),
+                    obs_uv=problem.obs_uv[src].copy(), cam_fixed=np.zeros(cam.size, np.uint8),
+                    cam_fixed_extr=np.zeros((cam.size, 16), np.float32),
+                    pt_fixed=None if problem.pt_fixed is None else problem.pt_fixed[pt].copy(),
+                    huber_a=problem.huber_a, name=f"{problem.name}/window{int(result.query[i])}")
+        for c in np.flatnonzero(result.win_cam_fixed[i]):
+            fix_camera(w, int(c))
+        out.append(w.normalized())
+    return out

@@ -13,8 +13,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as N
-from .problem import (ASSOC_DTYPE, FUSE_DTYPE, HUBER_A, MAP_POINT_DTYPE, MATCH_DTYPE, MATCH_KNN_DTYPE, AssocBatch,
-                      MapPointBatch, MatchBatch, Problem, WindowBatch, pack_match_batch, pack_window_batch)
+from .problem import (ASSOC_DTYPE, FUSE_DTYPE, GRAPH_FRAME_DTYPE, HUBER_A, MAP_POINT_DTYPE, MATCH_DTYPE, MATCH_KNN_DTYPE,
+                      AssocBatch, MapGraphResult, MapPointBatch, MapTable, MatchBatch, Problem, WindowBatch,
+                      pack_match_batch, pack_window_batch)
 
 
 def _ptr(a):
@@ -851,6 +852,79 @@ class Solver:
         fuse = np.zeros(max(nf, 1), FUSE_DTYPE)
         self._check(self.lib.ba_associate(self.h, C.byref(b), C.byref(p), _ptr(items), _ptr(fuse)), "ba_associate")
         return items[:ni].copy(), fuse[:nf].copy()
+
+    # -- covisibility lists, culling votes, local-BA windows ---------------------
+    _GRAPH_OPTIONS = ("th", "n_best", "order", "build_windows", "current_frame_id", "debug_tile_frames",
+                      "debug_chunk_queries", "reserved", "redundant_fraction")
+
+    def _map_table(self, table: MapTable):
+        t = table.normalized()
+        return t, N.ba_map_table(n_frames=t.n_frames, n_pts=t.n_pts, n_obs=t.n_obs, reserved=0, frame_id=_ptr(t.frame_id),
+                                 frame_is_key=_ptr(t.frame_is_key), pt_invalid=_ptr(t.pt_invalid),
+                                 pt_ref_frame=_ptr(t.pt_ref_frame), obs_offset=_ptr(t.obs_offset),
+                                 obs_frame=_ptr(t.obs_frame), obs_octave=_ptr(t.obs_octave), obs_outlier=_ptr(t.obs_outlier))
+
+    def _graph_options(self, fn: str, options: dict):
+        p = N.ba_graph_options()
+        self.lib.ba_map_graph_defaults(C.byref(p))
+        for key, val in options.items():
+            if key not in self._GRAPH_OPTIONS:
+                raise TypeError(f"{fn}: unknown option {key!r}")
+            setattr(p, key, float(val) if key == "redundant_fraction" else int(val))
+        return p
+
+    def map_graph(self, table: MapTable, queries, pt_status: bool = False, lists: bool = True, **options) -> MapGraphResult:
+        """Covisibility lists, culling votes and local-BA windows of the query
+        frames (ba_map_graph).  options: th, n_best, order, build_windows,
+        redundant_fraction, current_frame_id (read with pt_status), and the
+        debug fields (defaults: ba_map_graph_defaults).  Returns a
+        MapGraphResult: the records and, with `lists`, the lists split per
+        query (ba_map_graph_lists)."""
+        t, b = self._map_table(table)
+        p = self._graph_options("map_graph", options)
+        q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        nq = q.size
+        rec = np.zeros(max(nq, 1), GRAPH_FRAME_DTYPE)
+        status = np.zeros(max(t.n_pts, 1), np.uint8) if pt_status else None
+        self._check(self.lib.ba_map_graph(self.h, C.byref(b), _ptr(q), nq, C.byref(p), _ptr(rec), _ptr(status)),
+                    "ba_map_graph")
+        rec = rec[:nq].copy()
+        res = MapGraphResult(query=q, records=rec, nbr_frame=[], nbr_weight=[], win_cam=[], win_cam_fixed=[], win_pt=[],
+                             win_obs=[], win_obs_cam=[], win_obs_pt=[],
+                             pt_status=None if status is None else status[:t.n_pts].copy(), table=t)
+        if not lists:
+            return res
+        n_cam = rec["n_local"].astype(np.int64) + rec["n_fixed"]
+        counts = {"nbr_frame": rec["degree"], "nbr_weight": rec["degree"], "win_cam": n_cam, "win_cam_fixed": n_cam,
+                  "win_pt": rec["n_win_pts"], "win_obs": rec["n_win_obs"], "win_obs_cam": rec["n_win_obs"],
+                  "win_obs_pt": rec["n_win_obs"]}
+        flat = {k: np.zeros(max(int(np.sum(c, dtype=np.int64)), 1), np.uint8 if k == "win_cam_fixed" else np.int32)
+                for k, c in counts.items()}
+        out = N.ba_graph_lists(**{k: _ptr(a) for k, a in flat.items()})
+        self._check(self.lib.ba_map_graph_lists(self.h, C.byref(out)), "ba_map_graph_lists")
+        for k, c in counts.items():
+            cuts = np.cumsum(np.asarray(c, np.int64))
+            setattr(res, k, [a.copy() for a in np.split(flat[k][:int(cuts[-1]) if nq else 0], cuts[:-1])] if nq else [])
+        return res
+
+    def map_graph_weights(self, table: MapTable, frame: int, **options) -> np.ndarray:
+        """The raw weight row W_frame (n_frames,) int32 exactly as map_graph
+        forms it (ba_map_graph_weights)."""
+        t, b = self._map_table(table)
+        p = self._graph_options("map_graph_weights", options)
+        W = np.zeros(max(t.n_frames, 1), np.int32)
+        self._check(self.lib.ba_map_graph_weights(self.h, C.byref(b), int(frame), C.byref(p), _ptr(W)),
+                    "ba_map_graph_weights")
+        return W[:t.n_frames].copy()
+
+    def map_graph_times(self) -> np.ndarray:
+        """Times (ms) of the last map_graph: host preparation (wall), the
+        kernels (device), the whole call (wall)."""
+        n = self.lib.ba_map_graph_times(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            self.lib.ba_map_graph_times(self.h, _ptr(out), n)
+        return out
 
     def synchronize(self):
         self._check(self.lib.ba_synchronize(self.h), "ba_synchronize")

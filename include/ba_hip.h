@@ -1097,6 +1097,138 @@ void ba_associate_defaults(ba_assoc_options* opt);
 int ba_associate(ba_ctx* ctx, const ba_assoc_batch* batch, const ba_assoc_options* opt /* NULL = defaults */,
                  ba_assoc_result* items /* [n_items] */, ba_fuse_result* fuse /* [n_fuse] */);
 
+/* ba_map_graph: the covisibility lists, the culling votes and the local-BA
+ * windows of a batch of query frames, as a stateless function of a
+ * point-sorted observation table (the layout of ba_map_point_batch).  It
+ * restates Frame::updateCovisibilityGraph / getBestCovisibilityFrames
+ * (Frame.cpp:292-386), SfMHelper::cullRedundantKeyframes and the erase rule
+ * of cullRecentMapPoints / eraseOutlier (SfMHelper.cpp:974-1111) and the
+ * window of LocalBAOptimizerAngles (ba_optimizer.hpp:341-374) on indices.
+ * Everything is integers, so the result is exactly the restatement whatever
+ * the batching.  The table is expected to hold a (frame, point) pair at most
+ * once; it is not validated, and the rules are stated per observation, so
+ * duplicates still have a defined result.
+ *
+ * For a query frame q:
+ *   weights   for g != q, W_q[g] = the number of pairs (o, o') with
+ *             obs_frame[o] = q, obs_outlier[o] = 0, o' in the same track and
+ *             obs_frame[o'] = g.  pt_invalid and the outlier flag of o' are
+ *             not tested (Frame.cpp:301-321), so W is not symmetric once
+ *             outliers exist.
+ *   list L_q  the candidates are the g with W_q[g] > th (strict) and
+ *             frame_is_key[g].  No candidate but some W_q[g] > 0: the single
+ *             fallback g*, the lowest index among the largest weights, no
+ *             keyframe test (Frame.cpp:352-357), status BA_GRAPH_FALLBACK.
+ *             Every weight 0: the empty list, BA_GRAPH_ISOLATED (the
+ *             reference dereferences a null frame).  Else BA_GRAPH_OK.  The
+ *             list is ascending by the key W << 32 | g (the reference's ties
+ *             fall in pointer order, here in frame-index order).
+ *             degree = |L_q|, max_weight = the largest W_q[g] over all g.
+ *   best      the first min(n_best, |L_q|) entries of the list:
+ *             BA_GRAPH_WEAKEST_FIRST takes the ascending list (what the
+ *             reference does), BA_GRAPH_STRONGEST_FIRST the list by
+ *             descending weight, ties in ascending index (what it intends).
+ *   vote      n_map = the o with obs_frame[o] = q whose point is not invalid
+ *             (no outlier test).  Such an o is redundant when its track is
+ *             longer than 3 and at least 3 observations o' of the track have
+ *             obs_frame[o'] != q and obs_octave[o'] <= obs_octave[o] + 1.
+ *             cull = frame_id[q] is neither 0 nor 1 and
+ *             (double)n_map * redundant_fraction < (double)n_redundant
+ *             (SfMHelper.cpp:1019-1074; 0.95 is the code's value).
+ *   window    (build_windows != 0) local frames: the best frames in list
+ *             order, then q.  Local points: the p with pt_invalid[p] = 0 that
+ *             have a non-outlier observation by a local frame, ascending.
+ *             Fixed frames: the keyframes g, not local, with a non-outlier
+ *             observation of a local point, ascending.  Window observations:
+ *             the o of a local point with obs_outlier[o] = 0 and a local or
+ *             fixed frame, ascending (so sorted by point).  Window cameras:
+ *             the local frames, then the fixed frames; a camera's fixed flag
+ *             is set when it is a fixed frame or its frame_id is 0.
+ *   pt_status (when the array is given) with age = current_frame_id -
+ *             frame_id[pt_ref_frame[p]] and n the track length:
+ *             BA_GRAPH_PT_INVALID if pt_invalid[p], else BA_GRAPH_PT_ERASE if
+ *             age >= 4 && n <= 2, else BA_GRAPH_PT_MATURE if age >= 5, else
+ *             BA_GRAPH_PT_RECENT.
+ *
+ * A query's output depends only on the table, the options and q: not on its
+ * place in the batch, the other queries (duplicates are allowed), the column
+ * tile or the chunking.  Two calls give bitwise equal output.  The context's
+ * current problem is untouched, there is no collective, and the call blocks
+ * until the records are on the host.  The variable-length lists stay on the
+ * device until the next ba_map_graph or ba_destroy; ba_map_graph_lists copies
+ * them out.  An empty batch is valid.
+ *
+ * Errors: everything is validated on the host before anything is launched, and
+ * the message names the point, observation or query.
+ *   BA_ERR_INVALID_ARGUMENT  a NULL required array; negative counts;
+ *                            obs_offset[0] != 0 or a decreasing obs_offset; an
+ *                            obs_frame, pt_ref_frame or query out of range;
+ *                            n_best outside 0 .. BA_WINDOW_MAX_CAMS - 1; an
+ *                            unknown order; a negative th; a non-finite
+ *                            redundant_fraction; a negative debug field; a
+ *                            non-zero reserved field; pt_status without
+ *                            pt_ref_frame,
+ *   BA_ERR_OUT_OF_MEMORY     a buffer cannot be allocated. */
+typedef struct {
+  int32_t n_frames, n_pts, n_obs, reserved;
+  const int32_t *frame_id;       /* [n_frames] Frame::getID() */
+  const uint8_t *frame_is_key;   /* [n_frames]; NULL = all 1 */
+  const uint8_t *pt_invalid;     /* [n_pts]; NULL = all 0 */
+  const int32_t *pt_ref_frame;   /* [n_pts] frame index of the reference keyframe; NULL allowed without pt_status */
+  const int32_t *obs_offset;     /* [n_pts + 1]: point p owns observations [obs_offset[p], obs_offset[p+1]) */
+  const int32_t *obs_frame;      /* [n_obs] observing frame */
+  const int32_t *obs_octave;     /* [n_obs] keypoint octave; NULL = all 0 */
+  const uint8_t *obs_outlier;    /* [n_obs] Frame::isOutlier; NULL = all 0 */
+} ba_map_table;
+
+enum ba_graph_status { BA_GRAPH_OK = 0, BA_GRAPH_FALLBACK = 1, BA_GRAPH_ISOLATED = 2 };
+enum ba_graph_order { BA_GRAPH_WEAKEST_FIRST = 0, BA_GRAPH_STRONGEST_FIRST = 1 };
+enum ba_graph_pt_status { BA_GRAPH_PT_RECENT = 0, BA_GRAPH_PT_MATURE = 1, BA_GRAPH_PT_ERASE = 2, BA_GRAPH_PT_INVALID = 3 };
+
+typedef struct {
+  int32_t th;                  /* a covisibility edge needs more than th shared points; default 10 */
+  int32_t n_best;              /* default 10 */
+  int32_t order;               /* ba_graph_order; default BA_GRAPH_WEAKEST_FIRST */
+  int32_t build_windows;       /* default 1 */
+  int32_t current_frame_id;    /* read for pt_status only; default 0 */
+  int32_t debug_tile_frames;   /* column tile of the weight histogram; 0 = automatic */
+  int32_t debug_chunk_queries; /* queries per chunk; 0 = from the scratch budget */
+  int32_t reserved;            /* 0 */
+  double  redundant_fraction;  /* default 0.95 */
+} ba_graph_options;
+
+typedef struct {
+  int32_t status, degree, max_weight, n_map, n_redundant, cull, n_local, n_fixed, n_win_pts, n_win_obs;
+} ba_graph_frame;
+
+/* The variable-length results of the last successful ba_map_graph, query after
+ * query in query order; any array may be NULL.  Lengths (sums over the
+ * records): nbr_* sum(degree); win_cam* sum(n_local + n_fixed); win_pt
+ * sum(n_win_pts); win_obs* sum(n_win_obs).  win_obs is the index into the
+ * table; win_obs_cam and win_obs_pt are local to the window (positions in
+ * its win_cam and win_pt), the form ba_window_batch wants. */
+typedef struct {
+  int32_t *nbr_frame, *nbr_weight;
+  int32_t *win_cam;
+  uint8_t *win_cam_fixed;
+  int32_t *win_pt;
+  int32_t *win_obs, *win_obs_cam, *win_obs_pt;
+} ba_graph_lists;
+
+void ba_map_graph_defaults(ba_graph_options* opt);
+int ba_map_graph(ba_ctx* ctx, const ba_map_table* table, const int32_t* query /* [n_query] */, int n_query,
+                 const ba_graph_options* opt /* NULL = defaults */, ba_graph_frame* out /* [n_query] */,
+                 uint8_t* pt_status /* [n_pts] or NULL */);
+/* BA_ERR_INVALID_ARGUMENT before any successful ba_map_graph on the context. */
+int ba_map_graph_lists(ba_ctx* ctx, const ba_graph_lists* out);
+/* Test / inspection: the raw row W_frame[n_frames] (W[frame] = 0) exactly as
+ * ba_map_graph forms it; opt (NULL = defaults) is read for debug_tile_frames. */
+int ba_map_graph_weights(ba_ctx* ctx, const ba_map_table* table, int frame, const ba_graph_options* opt, int32_t* W);
+/* Times (ms) of the last successful ba_map_graph: [0] host preparation
+ * (wall), [1] the kernels (device), [2] the whole call (wall).  Copies
+ * min(n, 3) values and returns 3 (0 before the first call). */
+int ba_map_graph_times(ba_ctx* ctx, double* ms, int n);
+
 /* Test / inspection entry point: the state inside ceres::Solve's
  * SchurComplementSolver (Optimizer.cpp:242, DENSE_SCHUR) for one step.
  * Linearises at the current parameters with iteration-0 Jacobi scaling, then
