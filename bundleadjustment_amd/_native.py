@@ -200,6 +200,33 @@ class ba_match_neighbors(C.Structure):
     _fields_ = [("idx0", C.c_int32), ("idx1", C.c_int32), ("d2_0", C.c_float), ("d2_1", C.c_float)]
 
 
+class ba_icp_batch(C.Structure):
+    _fields_ = [
+        ("n_sets", C.c_int32), ("n_pairs", C.c_int32), ("set_offset", C.c_void_p), ("xyz", C.c_void_p),
+        ("pair_src", C.c_void_p), ("pair_tgt", C.c_void_p), ("guess", C.c_void_p),
+    ]
+
+
+class ba_icp_options(C.Structure):
+    _fields_ = [
+        ("max_iterations", C.c_int32), ("max_corr_dist", C.c_float), ("mse_abs_eps", C.c_double),
+        ("mse_rel_eps", C.c_double), ("transformation_eps", C.c_double), ("min_correspondences", C.c_int32),
+        ("with_scale", C.c_int32), ("fitness_max_range", C.c_float), ("route", C.c_int32), ("cell", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
+class ba_icp_result(C.Structure):
+    _fields_ = [
+        ("final", C.c_float * 16), ("converged", C.c_int32), ("state", C.c_int32), ("iterations", C.c_int32),
+        ("n_corr", C.c_int32), ("fitness", C.c_double),
+    ]
+
+
+ICP_ROUTE_AUTO, ICP_ROUTE_GRID, ICP_ROUTE_BRUTE = range(3)
+(ICP_NOT_CONVERGED, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES) = range(6)
+
+
 class ba_map_point_batch(C.Structure):
     _fields_ = [
         ("dim", C.c_int32), ("n_cams", C.c_int32), ("n_pts", C.c_int32), ("n_rows", C.c_int32),
@@ -389,6 +416,11 @@ SIGNATURES = [
     ("ba_map_graph_weights", C.c_int, [C.c_void_p, C.POINTER(ba_map_table), C.c_int, C.POINTER(ba_graph_options),
                                        C.c_void_p]),
     ("ba_map_graph_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ba_icp_defaults", None, [C.POINTER(ba_icp_options)]),
+    ("ba_icp", C.c_int, [C.c_void_p, C.POINTER(ba_icp_batch), C.POINTER(ba_icp_options), C.c_void_p, C.c_void_p]),
+    ("ba_icp_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ba_icp_nn", C.c_int, [C.c_void_p, C.POINTER(ba_icp_batch), C.c_int, C.POINTER(ba_icp_options), C.c_void_p,
+                            C.c_void_p]),
     ("ba_covariance", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request)]),
     ("ba_covariance_ex", C.c_int, [C.c_void_p, C.POINTER(ba_covariance_request_ex)]),
     ("ba_covariance_times", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

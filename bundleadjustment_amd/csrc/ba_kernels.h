@@ -533,6 +533,32 @@ void launch_map_graph_fill(const MapGraphArgs& A, hipStream_t s);      // the li
 void launch_map_graph_status(const MapGraphArgs& A, const int* pt_ref_frame, int current_frame_id, uint8_t* pt_status,
                              hipStream_t s);
 
+// batched point-to-point ICP: grid / sweep nearest neighbours, the Umeyama step (ba_icp.hip)
+struct IcpArgs {
+  int n_pair, max_ns;              // pairs; the largest source
+  int max_ring;                    // rings of the grid walk before a query goes to the sweep
+  float max_d2, fit_range;         // the gates of the loop's passes and of the fitness pass
+  IcpRules rules;
+  // inputs (IcpPlan)
+  const IcpPair* pair;             // [n_pair]
+  const IcpGrid* grid;
+  const int* cell_start;
+  const IcpPt* sorted;             // [points of all sets] the target sets in cell order
+  const float* xyz;                // [points of all sets][3]
+  const int* perm;                 // [NS] the order in which a pair's lanes take its source points
+  // state and scratch, per pair at IcpPair::soff / boff
+  IcpState* st;                    // [n_pair]
+  float* cur;                      // [NS][3]
+  int* idx;                        // [NS] the correspondence of this round (-1: not kept)
+  float* d2;                       // [NS]
+  int* flag;                       // [NS] the points left to the sweep, IcpState::n_flag of them
+  double* part;                    // [NB][kIcpSums] block partials
+  double* mse;                     // [n_pair][max_iter]
+};
+// round < max_iter: one iteration of every live pair; round == max_iter: the fitness pass.
+// nn_only: the correspondence pass alone (ba_icp_nn)
+void launch_icp_round(const IcpArgs& A, int round, bool nn_only, hipStream_t s);
+
 int grid_for(int n);
 int pt_group_grid(int np);   // grid of the kPtLanes-lanes-per-point kernels
 

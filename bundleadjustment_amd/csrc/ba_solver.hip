@@ -123,10 +123,10 @@ struct ba_ctx {
   unsigned* d_ticket = nullptr;  // k_reduce<true>'s last-workgroup ticket (zero between launches)
   unsigned scal_seq = 0;
   // staging of ba_solve_pose_batch, ba_solve_window_batch, ba_triangulate,
-  // ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors and
-  // ba_map_points_update / ba_associate (one each: a call of one never makes
+  // ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors,
+  // ba_map_points_update / ba_associate, ba_map_graph and ba_icp (one each: a call of one never makes
   // another reallocate)
-  StagingArena pose, win, tri, pnp, tv, match, mp, mg;
+  StagingArena pose, win, tri, pnp, tv, match, mp, mg, icp;
   GraphLists graph;                    // the lists of the last ba_map_graph (device)
   // ba_solve_window_batch: the last call's logs and times
   std::vector<ba_iteration> win_log;   // [n_problems][win_log_cap]
@@ -139,6 +139,7 @@ struct ba_ctx {
   std::vector<double> match_ms;        // ba_match_times of the last call
   std::vector<double> mp_ms;           // ba_map_points_times of the last call
   std::vector<double> mg_ms;           // ba_map_graph_times of the last call
+  std::vector<double> icp_ms;          // ba_icp_times of the last call
   hipEvent_t match_ev[3] = {nullptr, nullptr, nullptr};   // phase stamps of ba_match_descriptors (created by its first call)
 
   // host copies of the sorted structure, kept for the lazily built
@@ -2098,7 +2099,7 @@ int ba_destroy(ba_ctx* ctx) {
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
-  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv, &ctx->match, &ctx->mp, &ctx->mg}) (void)hipFree(a->dev);
+  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv, &ctx->match, &ctx->mp, &ctx->mg, &ctx->icp}) (void)hipFree(a->dev);
   for (char* b : ctx->graph.buf) (void)hipFree(b);
   for (hipEvent_t e : ctx->match_ev) if (e) (void)hipEventDestroy(e);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
@@ -3373,6 +3374,130 @@ int ba_map_graph_weights(ba_ctx* ctx, const ba_map_table* t, int frame, const ba
 
 int ba_map_graph_times(ba_ctx* ctx, double* ms, int n) {
   return ctx ? copy_times(ctx->mg_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
+}
+
+// ---------------------------------------------------------------------------
+// ba_icp / ba_icp_nn: host side.  Validation, the grids, the source
+// permutations and the section layout are plain C++ (check_icp, icp_plan,
+// icp_layout: host/ba_batch_pack.hpp); the tables go up through the staging
+// copy and the clouds from the caller's array, then max_iterations + 1 rounds
+// of ba_icp.hip with no sync in between and one download.  The context's
+// current problem is not touched.
+// ---------------------------------------------------------------------------
+void ba_icp_defaults(ba_icp_options* opt) {
+  if (opt) icp_defaults(*opt);
+}
+
+namespace {
+
+// the batch (pairs [first, first + n) of it) into the arena's host copy and
+// onto the device; the kernel arguments
+IcpArgs icp_stage(ba_ctx* ctx, const ba_icp_batch* b, const ba_icp_options& p, const IcpPlan& M, const IcpLayout& P,
+                  int first, const std::string& fn) {
+  const size_t N = M.pair.size(), total = (size_t)b->set_offset[b->n_sets];
+  if (N > 65535) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "more than 65535 pairs"};
+  HIP_OK(hipSetDevice(ctx->device));
+  ctx->icp.reserve(ctx, P.L.total, fn);
+  std::vector<char>& h = ctx->icp.host;
+  h.resize(P.L.io_b);
+  std::memset(h.data(), 0, P.xyz);
+  stage(h, P.pair, M.pair.data(), sizeof(IcpPair) * N);
+  stage(h, P.grid, M.grid.data(), sizeof(IcpGrid) * M.grid.size());
+  stage(h, P.cell_start, M.cell_start.data(), sizeof(int32_t) * M.cell_start.size());
+  stage(h, P.sorted, M.sorted.data(), sizeof(IcpPt) * total);
+  stage(h, P.perm, M.perm.data(), sizeof(int32_t) * M.NS);
+  IcpState* st = at<IcpState>(h.data(), P.st);
+  for (size_t i = 0; i < N; ++i) {
+    const IcpPair& Q = M.pair[i];
+    IcpState& S = st[i];
+    for (int e = 0; e < 16; ++e) S.fin[e] = b->guess && e < 12 ? b->guess[16 * (first + i) + e] : (e % 5 == 0 ? 1.0f : 0.0f);
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) S.M[3 * r + c] = S.fin[4 * r + c];
+      S.t[r] = S.fin[4 * r + 3];
+    }
+    S.state = BA_ICP_NOT_CONVERGED; S.converged = 0; S.iterations = 0; S.n_corr = 0;
+    S.apply_at = 0; S.n_flag = 0;
+    S.prev = DBL_MAX; S.fitness = DBL_MAX;
+    stage(h, P.cur + sizeof(float) * 3 * (size_t)Q.soff, b->xyz + 3 * (size_t)Q.s0, sizeof(float) * 3 * (size_t)Q.ns);
+  }
+  char* d = ctx->icp.dev;
+  HIP_OK(hipMemcpyAsync(d, h.data(), P.xyz, hipMemcpyHostToDevice, ctx->stream));
+  HIP_OK(hipMemcpyAsync(d + P.xyz, b->xyz, sizeof(float) * 3 * total, hipMemcpyHostToDevice, ctx->stream));
+  IcpArgs A{};
+  A.n_pair = (int)N; A.max_ns = M.max_ns; A.max_ring = kIcpMaxRing;
+  A.max_d2 = icp_gate(p.max_corr_dist); A.fit_range = p.fitness_max_range;
+  A.rules = IcpRules{p.max_iterations, p.min_correspondences, p.with_scale, p.mse_abs_eps, p.mse_rel_eps, p.transformation_eps};
+  A.pair = at<const IcpPair>(d, P.pair); A.grid = at<const IcpGrid>(d, P.grid);
+  A.cell_start = at<const int>(d, P.cell_start); A.sorted = at<const IcpPt>(d, P.sorted);
+  A.xyz = at<const float>(d, P.xyz); A.perm = at<const int>(d, P.perm);
+  A.st = at<IcpState>(d, P.st); A.cur = at<float>(d, P.cur); A.idx = at<int>(d, P.idx); A.d2 = at<float>(d, P.d2);
+  A.flag = at<int>(d, P.flag); A.part = at<double>(d, P.part); A.mse = at<double>(d, P.mse);
+  return A;
+}
+
+}  // namespace
+
+int ba_icp(ba_ctx* ctx, const ba_icp_batch* b, const ba_icp_options* opt, ba_icp_result* out, double* mse) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_icp: ";
+    const ba_icp_options p = check_icp(fn.c_str(), b, opt);
+    const size_t N = b->n_pairs;
+    if (N == 0) return;
+    if (!out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const double t0 = now_s();
+    const IcpPlan M = icp_plan(fn.c_str(), b, p, 0, (int)N);
+    const IcpLayout P = icp_layout(M, (size_t)b->set_offset[b->n_sets], p.max_iterations, false);
+    const IcpArgs A = icp_stage(ctx, b, p, M, P, 0, fn);
+    HIP_OK(hipMemsetAsync(A.mse, 0, sizeof(double) * N * (size_t)p.max_iterations, ctx->stream));
+    const double t_prep = now_s() - t0;
+    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
+    for (int round = 0; round <= p.max_iterations; ++round) launch_icp_round(A, round, false, ctx->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
+    std::vector<char>& h = ctx->icp.host;
+    char* d = ctx->icp.dev;
+    HIP_OK(hipMemcpyAsync(h.data() + P.st, d + P.st, sizeof(IcpState) * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    HIP_OK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    const IcpState* st = at<const IcpState>(h.data(), P.st);
+    for (size_t i = 0; i < N; ++i) {
+      ba_icp_result& R = out[i];
+      std::memcpy(R.final, st[i].fin, sizeof R.final);
+      R.converged = st[i].converged; R.state = st[i].state; R.iterations = st[i].iterations; R.n_corr = st[i].n_corr;
+      R.fitness = st[i].fitness;
+    }
+    if (mse) std::memcpy(mse, h.data() + P.mse, sizeof(double) * N * (size_t)p.max_iterations);
+    ctx->icp_ms = {1e3 * t_prep, (double)ms, 1e3 * (now_s() - t0), (double)ms / (p.max_iterations + 1)};
+  });
+}
+
+int ba_icp_times(ba_ctx* ctx, double* ms, int n) {
+  return ctx ? copy_times(ctx->icp_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
+}
+
+int ba_icp_nn(ba_ctx* ctx, const ba_icp_batch* b, int pair, const ba_icp_options* opt, int32_t* idx, float* d2) {
+  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    const std::string fn = "ba_icp_nn: ";
+    const ba_icp_options p = check_icp(fn.c_str(), b, opt);
+    if (pair < 0 || pair >= b->n_pairs)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " out of range"};
+    if (!idx || !d2) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
+    const IcpPlan M = icp_plan(fn.c_str(), b, p, pair, 1);
+    const IcpLayout P = icp_layout(M, (size_t)b->set_offset[b->n_sets], p.max_iterations, true);
+    const IcpArgs A = icp_stage(ctx, b, p, M, P, pair, fn);
+    launch_icp_round(A, 0, true, ctx->stream);
+    HIP_OK(hipGetLastError());
+    std::vector<char>& h = ctx->icp.host;
+    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, ctx->icp.dev + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost,
+                          ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(idx, h.data() + P.idx, sizeof(int32_t) * M.NS);
+    std::memcpy(d2, h.data() + P.d2, sizeof(float) * M.NS);
+  });
 }
 
 int ba_debug_blocks(ba_ctx* ctx, double radius, double* Hpp, double* gp, double* Hcc, double* gc, double* S,

@@ -1,13 +1,14 @@
 // ba_batch_pack.hpp — host-only packing shared by the batch entry points of
 // ba_solver.hip: the error type, the section layout of a staging buffer, the
 // CSR-offset validation, the summary record, the validation and layout of
-// ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors, ba_map_points_update, ba_associate and
-// ba_map_graph (with its plain restatement), and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
+// ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors, ba_map_points_update, ba_associate,
+// ba_map_graph (with its plain restatement) and ba_icp (with its grid plan), and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
 // plain C++17 without a HIP header and runs under ASan + UBSan
 // (tests/cpp/batch_pack.cpp, `make -C tests/cpp sanitize`).
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <limits>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "../../include/ba_hip.h"
+#include "../csrc/ba_icp.h"
 #include "../csrc/ba_map_graph.h"
 
 namespace bahip {
@@ -685,6 +687,218 @@ inline MapGraphHost map_graph_host(const ba_map_table* t, const MapGraphPlan& M,
                                                 t->obs_offset[pt + 1] - t->obs_offset[pt]);
   }
   return R;
+}
+
+// ---------------------------------------------------------------------------
+// ba_icp / ba_icp_nn
+// ---------------------------------------------------------------------------
+inline void icp_defaults(ba_icp_options& o) {
+  o.max_iterations = 10; o.max_corr_dist = std::numeric_limits<float>::infinity();
+  o.mse_abs_eps = 1e-12; o.mse_rel_eps = 0.0; o.transformation_eps = 0.0;
+  o.min_correspondences = 3; o.with_scale = 0; o.fitness_max_range = std::numeric_limits<float>::infinity();
+  o.route = BA_ICP_ROUTE_AUTO; o.cell = 0.0f; o.reserved = 0;
+}
+
+inline bool icp_finite(float v) { return v - v == 0.0f; }
+
+// Everything the kernels index with or branch on, checked on the host; the
+// options are returned with the defaults applied.
+inline ba_icp_options check_icp(const char* fn, const ba_icp_batch* b, const ba_icp_options* opt) {
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what}; };
+  if (!b || b->n_sets < 0 || b->n_pairs < 0) throw invalid("bad batch");
+  ba_icp_options p;
+  if (opt) p = *opt; else icp_defaults(p);
+  if (p.max_iterations < 1 || p.max_iterations > 10000) throw invalid("max_iterations must be in 1 .. 10000");
+  if (p.min_correspondences < 3) throw invalid("min_correspondences must be at least 3");
+  if (!(p.max_corr_dist >= 0.0f)) throw invalid("max_corr_dist must be non-negative");
+  if (!(p.fitness_max_range >= 0.0f)) throw invalid("fitness_max_range must be non-negative");
+  if (!(p.cell >= 0.0f) || !icp_finite(p.cell)) throw invalid("cell must be non-negative and finite");
+  if (p.mse_abs_eps != p.mse_abs_eps || p.mse_rel_eps != p.mse_rel_eps || p.transformation_eps != p.transformation_eps)
+    throw invalid("an epsilon is NaN");
+  if (p.with_scale != 0 && p.with_scale != 1) throw invalid("unknown with_scale " + std::to_string(p.with_scale));
+  if (p.route < BA_ICP_ROUTE_AUTO || p.route > BA_ICP_ROUTE_BRUTE) throw invalid("unknown route " + std::to_string(p.route));
+  if (p.reserved != 0) throw invalid("reserved must be 0");
+  if (b->n_sets > 0 && !b->set_offset) throw invalid("null array");
+  if (b->n_sets > 0) check_offsets(fn, "set_offset", b->set_offset, b->n_sets, "set");
+  const int total = b->n_sets > 0 ? b->set_offset[b->n_sets] : 0;
+  if (total > 0 && !b->xyz) throw invalid("null array");
+  for (int s = 0; s < b->n_sets; ++s)
+    for (int i = b->set_offset[s]; i < b->set_offset[s + 1]; ++i)
+      for (int a = 0; a < 3; ++a)
+        if (!icp_finite(b->xyz[3 * (size_t)i + a]))
+          throw invalid("set " + std::to_string(s) + " point " + std::to_string(i - b->set_offset[s]) + " is not finite");
+  if (b->n_pairs > 0 && (!b->pair_src || !b->pair_tgt)) throw invalid("null array");
+  for (int i = 0; i < b->n_pairs; ++i) {
+    const int ss = b->pair_src[i], st = b->pair_tgt[i];
+    if (ss < 0 || ss >= b->n_sets || st < 0 || st >= b->n_sets)
+      throw invalid("pair " + std::to_string(i) + " names a set out of range");
+    if (b->set_offset[ss + 1] - b->set_offset[ss] < 3)
+      throw invalid("pair " + std::to_string(i) + ": source set " + std::to_string(ss) + " has fewer than 3 points");
+    if (b->set_offset[st + 1] == b->set_offset[st])
+      throw invalid("pair " + std::to_string(i) + ": target set " + std::to_string(st) + " is empty");
+    if (b->guess)
+      for (int e = 0; e < 12; ++e)
+        if (!icp_finite(b->guess[16 * (size_t)i + e])) throw invalid("pair " + std::to_string(i) + ": guess is not finite");
+  }
+  return p;
+}
+
+// The grid of one target set: the geometry into G, the counting sort into
+// sorted[0 .. nt) and the cell_start run appended to cs.  The cell edge aims
+// at kIcpCellPts points per cell of the bounding box (an axis of zero extent
+// has one layer and does not count) and shrinks while the occupied cells hold
+// more than twice that, or is `cell` when that is positive; it grows until the
+// grid holds at most kIcpMaxCells cells.
+inline void icp_make_grid(const float* xyz, int nt, float cell, IcpGrid& G, IcpPt* sorted, std::vector<int32_t>& cs) {
+  float mn[3], mx[3];
+  for (int a = 0; a < 3; ++a) mn[a] = mx[a] = xyz[a];
+  for (int i = 1; i < nt; ++i)
+    for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], xyz[3 * (size_t)i + a]); mx[a] = std::max(mx[a], xyz[3 * (size_t)i + a]); }
+  double e[3], vol = 1.0, emax = 0.0;
+  int d = 0;
+  for (int a = 0; a < 3; ++a) {
+    e[a] = (double)mx[a] - (double)mn[a];
+    if (e[a] > 0.0) { vol *= e[a]; ++d; emax = std::max(emax, e[a]); }
+    G.mn[a] = mn[a];
+    G.c0[a] = (float)(0.5 * ((double)mn[a] + (double)mx[a]));
+  }
+  double h = cell > 0.0f ? (double)cell : d == 0 ? 1.0 : std::pow(vol * kIcpCellPts / (double)nt, 1.0 / d);
+  float hf = (float)h;
+  if (!(hf > 0.0f) || !icp_finite(hf)) hf = emax > 0.0 && (float)emax > 0.0f && icp_finite((float)emax) ? (float)emax : 1.0f;
+  G.pad = 0;
+  G.cell0 = (int32_t)cs.size();
+  std::vector<int32_t> cell_of((size_t)nt);
+  size_t nc = 0;
+  int32_t* start = nullptr;
+  for (int pass = 0;; ++pass) {
+    for (;;) {
+      double cells = 1.0;
+      for (int a = 0; a < 3; ++a) cells *= std::floor(e[a] / (double)hf) + 1.0;
+      if (cells <= (double)kIcpMaxCells) break;
+      hf *= 1.26f;
+    }
+    G.h = hf;
+    for (int a = 0; a < 3; ++a) G.n[a] = (int32_t)(std::floor(e[a] / (double)hf) + 1.0);
+    nc = (size_t)G.n[0] * G.n[1] * G.n[2];
+    cs.resize((size_t)G.cell0);
+    cs.resize((size_t)G.cell0 + nc + 1, 0);
+    start = cs.data() + G.cell0;
+    size_t occupied = 0;
+    for (int i = 0; i < nt; ++i) {
+      const float* q = xyz + 3 * (size_t)i;
+      const int c = (icp_cell(q[2], mn[2], hf, G.n[2]) * G.n[1] + icp_cell(q[1], mn[1], hf, G.n[1])) * G.n[0] +
+                    icp_cell(q[0], mn[0], hf, G.n[0]);
+      cell_of[(size_t)i] = c;
+      occupied += start[c + 1]++ == 0;
+    }
+    // A surface fills few cells of its box: while the occupied cells hold more than twice the aim, shrink the
+    // edge as for a sheet (occupied cells grow with 1 / h^2) and bin again, three times at the most.
+    if (cell > 0.0f || pass == 3 || (double)nt <= 2.0 * kIcpCellPts * (double)occupied) break;
+    const float next = hf * (float)std::sqrt((double)kIcpCellPts * (double)occupied / (double)nt);
+    if (!(next > 0.0f) || !(next < hf)) break;
+    hf = next;
+  }
+  for (size_t c = 0; c < nc; ++c) start[c + 1] += start[c];
+  std::vector<int32_t> fill(start, start + nc);
+  for (int i = 0; i < nt; ++i) {
+    const float* q = xyz + 3 * (size_t)i;
+    sorted[fill[(size_t)cell_of[(size_t)i]]++] = IcpPt{q[0], q[1], q[2], i};
+  }
+}
+
+// The grids (one per set that a pair of the plan names as its target, built
+// once), the pair table, and per GRID pair the permutation that walks the
+// source in the cell order of its initial position, so that a wavefront's
+// lanes visit the same cells (results are written at the original index).
+struct IcpPlan {
+  std::vector<IcpPair> pair;
+  std::vector<IcpGrid> grid;
+  std::vector<int32_t> cell_start;
+  std::vector<IcpPt> sorted;         // [points of all sets]; filled for the target sets
+  std::vector<int32_t> perm;         // [NS]
+  size_t NS = 0, NB = 0;             // source slots, block partials
+  int max_ns = 0;
+};
+inline IcpPlan icp_plan(const char* fn, const ba_icp_batch* b, const ba_icp_options& p, int first_pair, int n_pairs) {
+  IcpPlan M;
+  const size_t total = b->n_sets > 0 ? (size_t)b->set_offset[b->n_sets] : 0;
+  M.sorted.assign(total, IcpPt{0.0f, 0.0f, 0.0f, 0});
+  std::vector<int32_t> grid_of((size_t)std::max(b->n_sets, 0), -1);
+  M.pair.resize((size_t)n_pairs);
+  for (int i = 0; i < n_pairs; ++i) {
+    IcpPair& P = M.pair[(size_t)i];
+    const int ss = b->pair_src[first_pair + i], st = b->pair_tgt[first_pair + i];
+    P.s0 = b->set_offset[ss]; P.ns = b->set_offset[ss + 1] - P.s0;
+    P.t0 = b->set_offset[st]; P.nt = b->set_offset[st + 1] - P.t0;
+    if (grid_of[(size_t)st] < 0) {
+      grid_of[(size_t)st] = (int32_t)M.grid.size();
+      M.grid.emplace_back();
+      icp_make_grid(b->xyz + 3 * (size_t)P.t0, P.nt, p.cell, M.grid.back(), M.sorted.data() + P.t0, M.cell_start);
+    }
+    P.grid = grid_of[(size_t)st];
+    P.route = p.route != BA_ICP_ROUTE_AUTO ? p.route : P.nt <= kIcpBruteMax ? BA_ICP_ROUTE_BRUTE : BA_ICP_ROUTE_GRID;
+    P.soff = (int32_t)M.NS; P.boff = (int32_t)M.NB;
+    M.NS += (size_t)P.ns; M.NB += ((size_t)P.ns + kIcpThreads - 1) / kIcpThreads;
+    M.max_ns = std::max(M.max_ns, P.ns);
+    if (M.NS > 0x7fffffffull || M.cell_start.size() > 0x7fffffffull)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + "the pairs hold more than 2^31 - 1 source points or cells"};
+  }
+  M.perm.resize(M.NS);
+  std::vector<std::pair<int32_t, int32_t>> order;
+  for (int i = 0; i < n_pairs; ++i) {
+    const IcpPair& P = M.pair[(size_t)i];
+    int32_t* perm = M.perm.data() + P.soff;
+    if (P.route != BA_ICP_ROUTE_GRID) {
+      for (int q = 0; q < P.ns; ++q) perm[q] = q;
+      continue;
+    }
+    const IcpGrid& G = M.grid[(size_t)P.grid];
+    const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const float* g = b->guess ? b->guess + 16 * (size_t)(first_pair + i) : ident;
+    const float Mg[9] = {g[0], g[1], g[2], g[4], g[5], g[6], g[8], g[9], g[10]}, tg[3] = {g[3], g[7], g[11]};
+    order.resize((size_t)P.ns);
+    for (int q = 0; q < P.ns; ++q) {
+      const float* s = b->xyz + 3 * ((size_t)P.s0 + q);
+      float x = s[0], y = s[1], z = s[2];
+      icp_apply(Mg, tg, x, y, z);
+      const int c = (icp_cell(z, G.mn[2], G.h, G.n[2]) * G.n[1] + icp_cell(y, G.mn[1], G.h, G.n[1])) * G.n[0] +
+                    icp_cell(x, G.mn[0], G.h, G.n[0]);
+      order[(size_t)q] = {c, q};
+    }
+    std::sort(order.begin(), order.end());
+    for (int q = 0; q < P.ns; ++q) perm[q] = order[(size_t)q].second;
+  }
+  return M;
+}
+
+// The staging buffer: pair table, grids, cell_start, cell-sorted targets,
+// permutations, states (downloaded on their own), cur (the sources, pair by
+// pair), xyz | mse (or ba_icp_nn: idx, d2) | idx, d2, flagged queries, block
+// partials.
+struct IcpLayout {
+  SectionLayout L{256};
+  size_t pair = 0, grid = 0, cell_start = 0, sorted = 0, perm = 0, st = 0, cur = 0, xyz = 0;
+  size_t mse = 0, idx = 0, d2 = 0, flag = 0, part = 0;
+};
+inline IcpLayout icp_layout(const IcpPlan& M, size_t total, int max_iter, bool nn) {
+  IcpLayout P;
+  SectionLayout& L = P.L;
+  const size_t N = M.pair.size();
+  P.pair = L.add(sizeof(IcpPair) * N); P.grid = L.add(sizeof(IcpGrid) * M.grid.size());
+  P.cell_start = L.add(sizeof(int32_t) * M.cell_start.size()); P.sorted = L.add(sizeof(IcpPt) * total);
+  P.perm = L.add(sizeof(int32_t) * M.NS); P.st = L.add(sizeof(IcpState) * N); P.cur = L.add(sizeof(float) * 3 * M.NS);
+  P.xyz = L.add(sizeof(float) * 3 * total);   // the last input: uploaded from the caller's array
+  L.end_inputs();
+  if (nn) {
+    P.idx = L.add(sizeof(int32_t) * M.NS); P.d2 = L.add(sizeof(float) * M.NS);
+    L.end_outputs();
+  } else {
+    P.mse = L.add(sizeof(double) * N * (size_t)max_iter);
+    L.end_outputs();
+    P.idx = L.add(sizeof(int32_t) * M.NS); P.d2 = L.add(sizeof(float) * M.NS);
+  }
+  P.flag = L.add(sizeof(int32_t) * M.NS); P.part = L.add(sizeof(double) * kIcpSums * M.NB);
+  return P;
 }
 
 // One problem of ba_solve_window_batch as the kernel (ba_window.hip) reads it

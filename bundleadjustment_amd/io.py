@@ -1,4 +1,5 @@
-"""Problem I/O: BAL text format and the binary SoA dump.
+"""Problem I/O: BAL text format and the binary SoA dump;
+and PLY vertex clouds (``read_ply_vertices`` / ``write_ply_vertices``, at the end).
 
 Two exchange formats for problems in the reference's parameter layout
 (camera = [wx, wy, wz, tx, ty, tz] world->camera angle-axis + translation,
@@ -206,3 +207,88 @@ def write_bal(path: str | os.PathLike, problem: Problem) -> None:
             f.write(f"{float(-fx[c])!r}\n0.0\n0.0\n")
         for x in p.pts.reshape(-1):
             f.write(f"{float(x)!r}\n")
+
+
+# ---------------------------------------------------------------------------
+# PLY vertex clouds (the reference reads its ground-truth cloud from a PLY:
+# ReconstructionError.cpp:56).  Only the x, y, z properties of `element vertex`
+# are read; other properties and other elements are skipped.
+# ---------------------------------------------------------------------------
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply_vertices(path: str | os.PathLike) -> np.ndarray:
+    """The (n, 3) float32 vertex positions of an ASCII or binary_little_endian PLY."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data.index(b"\n", end) + 1
+    fmt, elements = None, []            # elements: [name, count, [(property, type | ("list", count type, item type))]]
+    for line in data[:end].decode("ascii", "replace").splitlines():
+        w = line.split()
+        if not w:
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append([w[1], int(w[2]), []])
+        elif w[0] == "property" and elements:
+            if w[1] == "list":
+                elements[-1][2].append((w[4], ("list", _PLY_TYPES[w[2]], _PLY_TYPES[w[3]])))
+            else:
+                elements[-1][2].append((w[2], _PLY_TYPES[w[1]]))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: unsupported PLY format {fmt!r}")
+    pos = body
+    lines = data[body:].decode("ascii", "replace").split("\n") if fmt == "ascii" else None
+    row = 0
+    for name, count, props in elements:
+        is_vertex = name == "vertex"
+        if is_vertex:
+            names = [p for p, _ in props]
+            if any(isinstance(t, tuple) for _, t in props) or not all(a in names for a in "xyz"):
+                raise ValueError(f"{path}: element vertex needs scalar x, y, z properties")
+        if fmt == "ascii":
+            if is_vertex:
+                cols = [names.index(a) for a in "xyz"]
+                rows = [ln.split() for ln in lines[row:row + count]]
+                if len(rows) != count or any(len(r) < len(props) for r in rows):
+                    raise ValueError(f"{path}: truncated vertex data")
+                return np.array([[float(r[c]) for c in cols] for r in rows], dtype=np.float64).astype(np.float32).reshape(-1, 3)
+            row += count
+        else:
+            if is_vertex:
+                dt = np.dtype([(p, "<" + t) for p, t in props])
+                if pos + count * dt.itemsize > len(data):
+                    raise ValueError(f"{path}: truncated vertex data")
+                v = np.frombuffer(data, dt, count, pos)
+                return np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32).reshape(-1, 3)
+            if all(not isinstance(t, tuple) for _, t in props):
+                pos += count * sum(np.dtype(t).itemsize for _, t in props)
+            else:
+                for _ in range(count):
+                    for _, t in props:
+                        if isinstance(t, tuple):
+                            k = int(np.frombuffer(data, "<" + t[1], 1, pos)[0])
+                            pos += np.dtype(t[1]).itemsize + k * np.dtype(t[2]).itemsize
+                        else:
+                            pos += np.dtype(t).itemsize
+    raise ValueError(f"{path}: no element vertex")
+
+
+def write_ply_vertices(path: str | os.PathLike, points, binary: bool = True) -> None:
+    """Write (n, 3) points as a PLY of float x, y, z vertices (binary_little_endian or ASCII)."""
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    head = ("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\nend_header\n"
+            .format("binary_little_endian" if binary else "ascii", pts.shape[0]))
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        if binary:
+            f.write(pts.astype("<f4").tobytes())
+        else:
+            # repr of a float32 round-trips exactly
+            f.write("".join("{} {} {}\n".format(*(repr(float(v)) for v in p)) for p in pts).encode("ascii"))

@@ -509,6 +509,39 @@ def pack_match_batch(sets, pairs, row_ref=None, ref_desc=None, dim: int | None =
                       pairs=np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2), row_ref=rr, ref_desc=rd)
 
 
+# one record of Solver.icp (ba_icp_result, include/ba_hip.h)
+ICP_RESULT_DTYPE = np.dtype([("final", np.float32, (4, 4)), ("converged", np.int32), ("state", np.int32),
+                             ("iterations", np.int32), ("n_corr", np.int32), ("fitness", np.float64)])
+
+
+@dataclass
+class IcpBatch:
+    """The arrays of the C-ABI's ba_icp_batch: set s owns points
+    [set_offset[s], set_offset[s+1]) of xyz; pair i aligns set pairs[i, 0]
+    (the source) to set pairs[i, 1] (the target)."""
+    set_offset: np.ndarray         # (S + 1,) int32
+    xyz: np.ndarray                # (points, 3) float32
+    pairs: np.ndarray              # (P, 2) int32: (source set, target set)
+    guess: np.ndarray | None       # (P, 4, 4) float32, row-major
+
+
+def pack_icp_batch(sets, pairs, guess=None) -> IcpBatch:
+    """Point clouds (a list of (n_s, 3) arrays) and (source set, target set)
+    index pairs as an IcpBatch.  guess: per pair a 4x4 initial transform of
+    the source, or None for the identity."""
+    sets = [np.asarray(s, dtype=np.float32).reshape(-1, 3) for s in sets]
+    off = np.zeros(len(sets) + 1, np.int64)
+    np.cumsum([s.shape[0] for s in sets], out=off[1:])
+    xyz = np.ascontiguousarray(np.concatenate(sets, axis=0) if sets else np.zeros((0, 3)), dtype=np.float32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    g = None
+    if guess is not None:
+        g = np.ascontiguousarray(guess, dtype=np.float32).reshape(-1, 4, 4)
+        if g.shape[0] != pairs.shape[0]:
+            raise ValueError("pack_icp_batch: guess needs one 4x4 per pair")
+    return IcpBatch(set_offset=off.astype(np.int32), xyz=xyz, pairs=pairs, guess=g)
+
+
 # one record of Solver.map_points_update (ba_map_point, include/ba_hip.h)
 MAP_POINT_DTYPE = np.dtype([("status", np.int32), ("best", np.int32), ("median", np.float32), ("view_dir", np.float32, 3),
                             ("min_dist", np.float32), ("max_dist", np.float32)])

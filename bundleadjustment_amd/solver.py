@@ -13,9 +13,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as N
-from .problem import (ASSOC_DTYPE, FUSE_DTYPE, GRAPH_FRAME_DTYPE, HUBER_A, MAP_POINT_DTYPE, MATCH_DTYPE, MATCH_KNN_DTYPE,
-                      AssocBatch, MapGraphResult, MapPointBatch, MapTable, MatchBatch, Problem, WindowBatch,
-                      pack_match_batch, pack_window_batch)
+from .problem import (ASSOC_DTYPE, FUSE_DTYPE, GRAPH_FRAME_DTYPE, HUBER_A, ICP_RESULT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE,
+                      MATCH_KNN_DTYPE, AssocBatch, IcpBatch, MapGraphResult, MapPointBatch, MapTable, MatchBatch, Problem,
+                      WindowBatch, pack_icp_batch, pack_match_batch, pack_window_batch)
 
 
 def _ptr(a):
@@ -777,6 +777,69 @@ class Solver:
         out = np.empty(max(n, 0))
         if n > 0:
             self.lib.ba_match_times(self.h, _ptr(out), n)
+        return out
+
+    # -- point-cloud ICP -------------------------------------------------------
+    _ICP_OPTIONS = {"max_iterations": int, "max_corr_dist": float, "mse_abs_eps": float, "mse_rel_eps": float,
+                    "transformation_eps": float, "min_correspondences": int, "with_scale": int,
+                    "fitness_max_range": float, "route": int, "cell": float}
+
+    def _icp_batch(self, ib: IcpBatch, icp_options: dict, who: str):
+        ps = np.ascontiguousarray(ib.pairs[:, 0])
+        pt = np.ascontiguousarray(ib.pairs[:, 1])
+        b = N.ba_icp_batch(n_sets=ib.set_offset.size - 1, n_pairs=ib.pairs.shape[0], set_offset=_ptr(ib.set_offset),
+                           xyz=_ptr(ib.xyz), pair_src=_ptr(ps), pair_tgt=_ptr(pt), guess=_ptr(ib.guess))
+        p = N.ba_icp_options()
+        self.lib.ba_icp_defaults(C.byref(p))
+        for key, val in icp_options.items():
+            if key not in self._ICP_OPTIONS:
+                raise TypeError(f"{who}: unknown option {key!r}")
+            if key == "route" and isinstance(val, str):
+                val = {"AUTO": N.ICP_ROUTE_AUTO, "GRID": N.ICP_ROUTE_GRID, "BRUTE": N.ICP_ROUTE_BRUTE}[val]
+            setattr(p, key, self._ICP_OPTIONS[key](val))
+        return b, p, (ps, pt, ib)
+
+    def icp(self, sets, pairs=None, guess=None, **icp_options) -> tuple[np.ndarray, np.ndarray]:
+        """Batched point-to-point ICP and its fitness score (ba_icp): exact
+        nearest neighbours, the Umeyama step and PCL's convergence rules, on
+        the device.  sets: an IcpBatch, or a list of (n_s, 3) float32 clouds
+        with pairs (P, 2) of (source set, target set) indices and an optional
+        guess (P, 4, 4).  icp_options: max_iterations, max_corr_dist,
+        mse_abs_eps, mse_rel_eps, transformation_eps, min_correspondences,
+        with_scale, fitness_max_range, route ("AUTO" / "GRID" / "BRUTE"), cell
+        (defaults: ba_icp_defaults).  Returns (an ICP_RESULT_DTYPE record
+        array (P,), mse (P, max_iterations))."""
+        ib = sets if isinstance(sets, IcpBatch) else pack_icp_batch(sets, pairs, guess)
+        b, p, _keep = self._icp_batch(ib, icp_options, "icp")
+        n = ib.pairs.shape[0]
+        out = np.zeros(max(n, 1), ICP_RESULT_DTYPE)
+        mse = np.zeros((max(n, 1), max(int(p.max_iterations), 1)))
+        self._check(self.lib.ba_icp(self.h, C.byref(b), C.byref(p), _ptr(out), _ptr(mse)), "ba_icp")
+        return out[:n].copy(), mse[:n].copy()
+
+    def icp_nn(self, sets, pairs=None, guess=None, pair: int = 0, **icp_options) -> tuple[np.ndarray, np.ndarray]:
+        """One correspondence pass of one pair on guess * source through the
+        route the options select (ba_icp_nn): (idx (n_src,) int32 with -1 for
+        a point that is not kept, d2 (n_src,) float32)."""
+        ib = sets if isinstance(sets, IcpBatch) else pack_icp_batch(sets, pairs, guess)
+        b, p, _keep = self._icp_batch(ib, icp_options, "icp_nn")
+        ns = 0
+        if 0 <= int(pair) < ib.pairs.shape[0]:
+            s = int(ib.pairs[int(pair), 0])
+            if 0 <= s < ib.set_offset.size - 1:
+                ns = max(int(ib.set_offset[s + 1] - ib.set_offset[s]), 0)
+        idx = np.zeros(max(ns, 1), np.int32)
+        d2 = np.zeros(max(ns, 1), np.float32)
+        self._check(self.lib.ba_icp_nn(self.h, C.byref(b), int(pair), C.byref(p), _ptr(idx), _ptr(d2)), "ba_icp_nn")
+        return idx[:ns].copy(), d2[:ns].copy()
+
+    def icp_times(self) -> np.ndarray:
+        """Times (ms) of the last icp: host preparation (wall), the kernels
+        (device), the whole call (wall), the kernels per enqueued round."""
+        n = self.lib.ba_icp_times(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            self.lib.ba_icp_times(self.h, _ptr(out), n)
         return out
 
     # -- map-point upkeep and association gates --------------------------------

@@ -1229,6 +1229,144 @@ int ba_map_graph_weights(ba_ctx* ctx, const ba_map_table* table, int frame, cons
  * min(n, 3) values and returns 3 (0 before the first call). */
 int ba_map_graph_times(ba_ctx* ctx, double* ms, int n);
 
+/* ---------------------------------------------------------------------------
+ * ba_icp: batched point-to-point ICP of point clouds and its fitness score:
+ * the arithmetic behind the reference's reconstruction error
+ * (ReconstructionError.cpp:134-190: pcl::IterativeClosestPoint with every
+ * default, align, hasConverged, getFitnessScore).  PCL was not available where
+ * this was written: the rules below restate PCL 1.12's documented defaults as
+ * recalled and are pinned here (csrc/ba_icp.h is the text, the same on the
+ * device and in host programs); INTEGRATION.md lists what to verify against a
+ * PCL build.  PCL's kd-tree search is exact, so the exact nearest neighbour is
+ * what is pinned.
+ *
+ * Batch.  n_sets clouds in CSR form: set s owns points
+ * [set_offset[s], set_offset[s+1]) of xyz (3 floats per point).  Pair i aligns
+ * the points of set pair_src[i] (the source) to those of set pair_tgt[i] (the
+ * target); a set may appear in any number of pairs and is uploaded once.
+ * guess: per pair a float 4x4, row-major, applied to the source first (its
+ * first three rows are read; the last is taken as 0 0 0 1); NULL = identity.
+ *
+ * Per iteration, on cur (float; cur_0 = guess * source):
+ *  1. Correspondences.  For a source point p and a target point q (float,
+ *     every operation rounded on its own, nothing contracted):
+ *       d2 = ((dx*dx + dy*dy) + dz*dz),   dx = p.x - q.x, ...
+ *     The neighbour of p is the target index j of smallest key
+ *     (bits(d2) << 32 | j): ties go to the lowest index.  p is kept iff
+ *     d2 <= max_corr_dist * max_corr_dist (a float product); a point that is
+ *     not kept has index -1 and d2 = +inf.
+ *  2. Fewer than min_correspondences kept: state NO_CORRESPONDENCES,
+ *     converged = 0, the loop stops (iterations is not advanced).
+ *  3. Rigid estimate (Umeyama; TransformationEstimationSVD), fp64: sums of
+ *     a = cur - c0 and b = target - c0 (c0: the centre of the target's bounding
+ *     box) over the kept points in a fixed order; means ma, mb;
+ *     H = sum b a^T - n mb ma^T = U diag(s) V^T by one-sided Jacobi with U, V
+ *     rotations (the reflection case carries its sign on the smallest singular
+ *     value, which is Umeyama's sign matrix); R = U V^T;
+ *     c = (s0 + s1 +- s2) / (sum |a|^2 - n |ma|^2) with with_scale, else 1;
+ *     t = (c0 + mb) - c R (c0 + ma).  c R and t are rounded to float.  A
+ *     non-finite R (the kept source points are collinear) is replaced by the
+ *     identity with c = 1.
+ *  4. Update.  cur <- (c R) cur + t as ((m0*x + m1*y) + m2*z) + t per row, and
+ *     final <- T_k final as a float 4x4 product, terms in ascending k (final
+ *     starts as the guess).
+ *  5. Convergence (DefaultConvergenceCriteria), in this order, after
+ *     iterations += 1:
+ *       iterations >= max_iterations                        -> ITERATIONS
+ *       (tr(cR) - 1) / 2 >= 1 - transformation_eps and
+ *         |t|^2 <= transformation_eps (fp64 of the floats)  -> TRANSFORM
+ *       mse = fp64 mean of the kept float d2;
+ *       |mse - prev| < mse_abs_eps                          -> ABS_MSE
+ *       mse_rel_eps > 0 and |mse - prev| / prev < mse_rel_eps -> REL_MSE
+ *     each with converged = 1; otherwise prev = mse (initially DBL_MAX).
+ *     mse[k] of iteration k is recorded whichever rule ends the loop.
+ *
+ * Fitness (getFitnessScore).  For a converged pair, one more correspondence
+ * pass on the final cur: the fp64 mean of d2 over the points with
+ * d2 <= fitness_max_range, DBL_MAX when there is none.  A pair that did not
+ * converge has fitness DBL_MAX (the reference reports its maximum there).
+ *
+ * Search.  Targets above a size threshold (route AUTO) are searched through a
+ * uniform grid over the target's bounding box, built once on the host; the
+ * ring walk stops only when every unvisited cell is provably farther than the
+ * best key found, so GRID, BRUTE and every cell size give the same bits.
+ * cell > 0 overrides the grid's cell size (debug).
+ *
+ * Contract, as ba_match_descriptors: a pair's output bits depend only on its
+ * own data and the options, not on its place in the batch, on the other
+ * pairs, on route or on cell; two calls give bitwise equal output; no float
+ * atomics; the context's current problem is untouched; no collective; the
+ * call blocks until the results are on the host.  An empty batch is valid.
+ *
+ * Errors (the context stays usable; nothing is launched; all validation is on
+ * the host; the message names the culprit):
+ *   BA_ERR_INVALID_ARGUMENT  a NULL required array, negative counts, a bad
+ *                            set_offset, a pair's set index out of range, a
+ *                            source of fewer than 3 points, an empty target,
+ *                            a non-finite coordinate (the message names the
+ *                            set and the point) or guess, max_iterations < 1
+ *                            or > 10000, min_correspondences < 3, a negative
+ *                            or NaN max_corr_dist / fitness_max_range / cell,
+ *                            a NaN epsilon, with_scale other than 0 / 1, an
+ *                            unknown route, reserved != 0,
+ *   BA_ERR_OUT_OF_MEMORY     the scratch cannot be allocated. */
+#define BA_ICP_ROUTE_AUTO 0
+#define BA_ICP_ROUTE_GRID 1
+#define BA_ICP_ROUTE_BRUTE 2
+/* ba_icp_result.state (PCL's ConvergenceState) */
+#define BA_ICP_NOT_CONVERGED 0
+#define BA_ICP_ITERATIONS 1
+#define BA_ICP_TRANSFORM 2
+#define BA_ICP_ABS_MSE 3
+#define BA_ICP_REL_MSE 4
+#define BA_ICP_NO_CORRESPONDENCES 5
+
+typedef struct {
+  int32_t n_sets, n_pairs;
+  const int32_t* set_offset;     /* [n_sets+1], [0] = 0, non-decreasing: points of xyz */
+  const float*   xyz;            /* [3 * points] */
+  const int32_t* pair_src;       /* [n_pairs] set index of the source */
+  const int32_t* pair_tgt;       /* [n_pairs] set index of the target */
+  const float*   guess;          /* [n_pairs][16] row-major, or NULL = identity */
+} ba_icp_batch;
+
+typedef struct {
+  int32_t max_iterations;        /* default 10 */
+  float   max_corr_dist;         /* default +inf (PCL: sqrt(DBL_MAX), which rejects nothing) */
+  double  mse_abs_eps;           /* default 1e-12 */
+  double  mse_rel_eps;           /* default 0: <= 0 is off (PCL: euclidean_fitness_epsilon = -DBL_MAX) */
+  double  transformation_eps;    /* default 0 */
+  int32_t min_correspondences;   /* default 3 */
+  int32_t with_scale;            /* default 0 */
+  float   fitness_max_range;     /* default +inf; compared with d2 */
+  int32_t route;                 /* default BA_ICP_ROUTE_AUTO */
+  float   cell;                  /* default 0: the planned cell size; > 0 overrides it (never changes a result bit) */
+  int32_t reserved;              /* 0 */
+} ba_icp_options;
+
+typedef struct {
+  float   final[16];             /* row-major 4x4: the guess times every step */
+  int32_t converged, state;
+  int32_t iterations, n_corr;    /* n_corr: kept correspondences of the last iteration */
+  double  fitness;
+} ba_icp_result;
+
+void ba_icp_defaults(ba_icp_options* opt);
+/* mse: [n_pairs][max_iterations] (entries past a pair's iterations are 0), or NULL */
+int ba_icp(ba_ctx* ctx, const ba_icp_batch* batch, const ba_icp_options* opt /* NULL = defaults */,
+           ba_icp_result* out /* [n_pairs] */, double* mse);
+/* Times (ms) of the last successful ba_icp: [0] host preparation (wall: the
+ * checks, the grids, the source permutations), [1] the kernels (device),
+ * [2] the whole call (wall), [3] [1] per enqueued round (max_iterations + 1).
+ * As ba_match_times otherwise. */
+int ba_icp_times(ba_ctx* ctx, double* ms, int n);
+/* Test / inspection entry point, in the role of ba_match_knn: one
+ * correspondence pass of pair `pair` on guess * source through the route the
+ * options select (opt NULL = defaults; route, cell and max_corr_dist are
+ * read): idx[n_src] (-1: not kept) and d2[n_src].  Same errors as ba_icp, plus
+ * a pair out of range. */
+int ba_icp_nn(ba_ctx* ctx, const ba_icp_batch* batch, int pair, const ba_icp_options* opt, int32_t* idx, float* d2);
+
 /* Test / inspection entry point: the state inside ceres::Solve's
  * SchurComplementSolver (Optimizer.cpp:242, DENSE_SCHUR) for one step.
  * Linearises at the current parameters with iteration-0 Jacobi scaling, then
