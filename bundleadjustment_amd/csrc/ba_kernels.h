@@ -294,9 +294,7 @@ void launch_pose_batch(int nprob, const int* off, const double* cams_in, const f
 // per problem (ba_window.hip).  All index arrays are local to their problem;
 // observations sorted by (point, camera).
 constexpr int kWinMaxCams = 16;    // = BA_WINDOW_MAX_CAMS: variable observed cameras per problem
-// doubles per camera table row, value-only camera record and observation
-// record of the scratch (= kTblRec, kRecL, kJR of the device headers)
-constexpr int kWinTbl = 42, kWinVRec = 48, kWinJR = 20;
+// (kWinTbl, kWinVRec, kWinJR, the record sizes of the scratch: host/ba_batch_pack.hpp, with the layout)
 struct WinArgs {
   const WinProb* prob;
   size_t NC, NP, NO, NV;           // totals over the batch (strides of the double-buffered scratch)
@@ -335,7 +333,7 @@ int launch_window_batch(int nprob, const WinArgs& A, const PoseOpts& o, size_t l
 // (ba_triangulate.hip): kTriGroup lanes per point, one launch plus the
 // per-camera prologue
 constexpr int kTriGroup = 8;       // lanes per point: a compile-time constant, never chosen from the batch
-constexpr int kTriRec = 64;        // doubles per camera of the scratch: value-only record [0, 48), K-folded table [48, 64)
+// (kTriRec, doubles per camera of the scratch: host/ba_batch_pack.hpp, with the layout)
 struct TriArgs {
   int n_pts, n_cams;
   int init_given, refine, min_views, checks, behind_any;

@@ -1,8 +1,7 @@
 // ba_solver.hip — host side of libba_hip.so: problem structure, device
-// workspace, the Levenberg-Marquardt driver and the extern "C" ABI
-// (include/ba_hip.h).  The batch entry points stage through StagingArena; their
-// host-only packing (the error type, section layout, offset checks, the window
-// structure build) is host/ba_batch_pack.hpp.
+// workspace, the Levenberg-Marquardt driver, covariance, the debug entries, the
+// communicator and create / destroy of the extern "C" ABI (include/ba_hip.h).
+// The context is ba_ctx.h; the batch entry points are ba_batch.hip.
 //
 // The driver restates ceres::TrustRegionMinimizer + LevenbergMarquardtStrategy
 // with the options of BAOptimizer::configureSolver (reference
@@ -16,348 +15,20 @@
 // per-camera blocks after linearisation, the dense reduced camera system
 // after point elimination, and the scalar record after the candidate pass.
 // All ranks then take identical decisions.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <numeric>
-#include <stdexcept>
-#include <string>
-#include <vector>
 
-#include "../../include/ba_hip.h"
+#include "ba_ctx.h"
 #include "ba_device.h"
-#include "ba_cov_pcg.h"
-#include "ba_kernels.h"
 
 using namespace bahip;
 
 namespace {
 
-// BaError {code, msg}: host/ba_batch_pack.hpp (through ba_kernels.h)
-#define HIP_OK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      throw BaError{_e == hipErrorOutOfMemory ? BA_ERR_OUT_OF_MEMORY : BA_ERR_DEVICE,                 \
-                    std::string(#expr) + ": " + hipGetErrorString(_e)};                               \
-  } while (0)
-#define NCCL_OK(expr)                                                                                 \
-  do {                                                                                                \
-    ncclResult_t _r = (expr);                                                                         \
-    if (_r != ncclSuccess) throw BaError{BA_ERR_COMM, std::string(#expr) + ": " + ncclGetErrorString(_r)}; \
-  } while (0)
-
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// One staging buffer of a batch entry point: device memory (inputs | outputs |
-// scratch) grown on demand and reused across calls, and the host copy of its
-// inputs / outputs
-struct StagingArena {
-  char* dev = nullptr;
-  size_t cap = 0;
-  std::vector<char> host;
-  void reserve(ba_ctx* ctx, size_t bytes, const std::string& fn);
-};
-
-// The variable-length lists of the last ba_map_graph, on the device: the eight
-// arrays of ba_graph_lists in its order, grown chunk by chunk.  len: elements
-// of the neighbour, camera, point and observation lists.
-struct GraphLists {
-  static constexpr int kArrays = 8;
-  static constexpr size_t elem[kArrays] = {4, 4, 4, 1, 4, 4, 4, 4};
-  static constexpr int kind[kArrays] = {0, 0, 1, 1, 2, 3, 3, 3};
-  char* buf[kArrays] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t cap[kArrays] = {0, 0, 0, 0, 0, 0, 0, 0};   // elements
-  size_t len[4] = {0, 0, 0, 0};
-  bool valid = false;
-};
-
 // hipFree at scope exit (buffers that live for one call)
 struct DevFree { void* p; ~DevFree() { (void)hipFree(p); } };
-
-}  // namespace
-
-struct ba_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [2..5]: two r+J stamp pairs, [6]: scalar blit
-  int rj_slot = 0;   // the stamp pair of the next timed linearisation (bench)
-  // the device linearisation state is at the candidate of the last step (a
-  // speculative linearisation, enqueued behind the step's scalar record)
-  bool lin_at_cand = false;
-
-  // multi-GPU
-  int nranks = 1, rank = 0;
-  ncclComm_t comm = nullptr;
-  // host-staged transport (ba_comm_init_host: tests of the multi-rank path
-  // with several ranks on one GPU, where RCCL refuses duplicate devices)
-  ba_host_allreduce_fn host_fn = nullptr;
-  void* host_user = nullptr;
-  std::vector<double> host_buf;
-
-  // problem
-  bool have_problem = false;
-  int nc = 0, np = 0, no = 0, nvc = 0, n = 0, ld = 0;
-  std::vector<int> perm;         // sorted obs -> caller obs
-  std::vector<int> chol_off;     // split Cholesky task table: host step offsets (W.ctask_off)
-  std::vector<int> cam_of_vc;
-  std::vector<uint8_t> cam_fixed_h, pt_fixed_h;
-  double huber_a = 0.0;
-  DevProblem P{};
-  DevWork W{};
-  std::vector<void*> allocs;     // device buffers of the current problem
-  double* h_scal = nullptr;      // pinned scalar record (device-mapped, coherent)
-  double* d_hscal = nullptr;     // its device address
-  unsigned* h_seq = nullptr;     // the record's sequence number (after the record), host / device address
-  unsigned* d_hseq = nullptr;
-  unsigned* d_ticket = nullptr;  // k_reduce<true>'s last-workgroup ticket (zero between launches)
-  unsigned scal_seq = 0;
-  // staging of ba_solve_pose_batch, ba_solve_window_batch, ba_triangulate,
-  // ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors,
-  // ba_map_points_update / ba_associate, ba_map_graph and ba_icp (one each: a call of one never makes
-  // another reallocate)
-  StagingArena pose, win, tri, pnp, tv, match, mp, mg, icp;
-  GraphLists graph;                    // the lists of the last ba_map_graph (device)
-  // ba_solve_window_batch: the last call's logs and times
-  std::vector<ba_iteration> win_log;   // [n_problems][win_log_cap]
-  std::vector<int> win_log_n;
-  int win_log_cap = 0;
-  std::vector<double> win_ms;          // ba_window_times of the last call
-  std::vector<double> tri_ms;          // ba_triangulate_times of the last call
-  std::vector<double> pnp_ms;          // ba_pnp_times of the last call
-  std::vector<double> tv_ms;           // ba_two_view_times of the last call
-  std::vector<double> match_ms;        // ba_match_times of the last call
-  std::vector<double> mp_ms;           // ba_map_points_times of the last call
-  std::vector<double> mg_ms;           // ba_map_graph_times of the last call
-  std::vector<double> icp_ms;          // ba_icp_times of the last call
-  hipEvent_t match_ev[3] = {nullptr, nullptr, nullptr};   // phase stamps of ba_match_descriptors (created by its first call)
-
-  // host copies of the sorted structure, kept for the lazily built
-  // linear-solver structures (Schur pair lists / PCG duplicate pairs)
-  std::vector<int> h_pt_off, h_obs_cam, h_vc;
-  std::vector<uint8_t> h_pt_var;
-  bool have_dense = false, have_pcg = false;
-  int chol_epoch = 0;   // launches of the back substitution (hand-off flag values)
-  // scalar slots whose fold a linearisation left to the step enqueued right
-  // behind it (single rank: one k_reduce for both records)
-  uint32_t pend_sum = 0, pend_max = 0;
-  // the camera-side norms pass of such a linearisation, left to ride in the
-  // step's point-elimination launch (launch_point_elim's NormsFold)
-  bool norms_pend = false;
-  bahip::NormsFold norms_args{};
-  // a pending norms pass as its own launch (before any fold of its slots)
-  void flush_norms() {
-    if (!norms_pend) return;
-    norms_pend = false;
-    bahip::launch_cam_norms(P, W, norms_args.compute_scale != 0, norms_args.min_diag, norms_args.max_diag, stream);
-  }
-  const bahip::NormsFold* take_norms() {
-    if (!norms_pend) return nullptr;
-    norms_pend = false;
-    return &norms_args;
-  }
-  void clear_pending() { pend_sum = pend_max = 0; norms_pend = false; }
-  bool dup_diag = false;   // the dense pair list has diagonal blocks (duplicate observations)
-  bool k_plain = false;    // every camera's K without skew, row 2 = (0, 0, k22) (set_problem)
-  size_t pcg_ndup = 0;     // ITERATIVE_SCHUR duplicate (camera, point) pairs (ensure_pcg)
-  double* tobs_buf = nullptr;   // [no][6] ITERATIVE_SCHUR per-observation products (allocated on first use)
-  int max_no = 0;               // largest observation count over the ranks (collective matvec-path choice)
-  // ba_covariance_iterative: the multi-column CG's scratch (allocated on first
-  // use, grown on demand, freed with the problem) and its capacity in columns
-  bahip::McgBufs mcg{};
-  int mcg_cols = 0;
-
-  // solver state
-  std::vector<ba_iteration> log;
-  std::vector<double> bench_ms;   // host wall time of each iteration of the last ba_bench_iterations
-  std::vector<double> cov_ms;     // device time of the phases of the last ba_covariance
-  bool scale_valid = false;
-  double t_lin = 0.0, t_solve = 0.0;
-
-  template <typename T>
-  T* dalloc(size_t count) {
-    if (count == 0) count = 1;
-    void* p = nullptr;
-    HIP_OK(hipMalloc(&p, count * sizeof(T)));
-    allocs.push_back(p);
-    return static_cast<T*>(p);
-  }
-  void dfree(void* p) {
-    if (!p) return;
-    auto it = std::find(allocs.begin(), allocs.end(), p);
-    if (it != allocs.end()) allocs.erase(it);
-    if (stream) (void)hipStreamSynchronize(stream);
-    (void)hipFree(p);
-  }
-  template <typename T>
-  T* upload(const std::vector<T>& v) {
-    T* d = dalloc<T>(v.size());
-    if (!v.empty()) HIP_OK(hipMemcpyAsync(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-    return d;
-  }
-  void free_problem() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (void* p : allocs) (void)hipFree(p);
-    allocs.clear();
-    have_problem = have_dense = have_pcg = false;
-    tobs_buf = nullptr;
-    mcg = bahip::McgBufs{};
-    mcg_cols = 0;
-    scale_valid = false;
-    log.clear();
-  }
-
-  // collectives on the data path: with more than one rank, or forced on a
-  // one-rank communicator (BA_FORCE_COLLECTIVES=1: tests of the exchange path
-  // on a single GPU, where the all-reduce is the identity)
-  bool force_coll = false;
-  bool has_comm() const { return comm || host_fn; }
-  bool coll() const { return has_comm() && (nranks > 1 || force_coll); }
-  void allreduce(double* d, size_t count, ncclRedOp_t op = ncclSum) {
-    if (!has_comm() || count == 0) return;   // a 1-rank communicator still runs the collectives (tests)
-    if (host_fn) {   // stage through the host and the caller's transport
-      host_buf.resize(count);
-      HIP_OK(hipMemcpyAsync(host_buf.data(), d, sizeof(double) * count, hipMemcpyDeviceToHost, stream));
-      HIP_OK(hipStreamSynchronize(stream));
-      if (host_fn(host_user, host_buf.data(), (int64_t)count, op == ncclMax ? 1 : 0) != 0)
-        throw BaError{BA_ERR_COMM, "host all-reduce callback failed"};
-      HIP_OK(hipMemcpyAsync(d, host_buf.data(), sizeof(double) * count, hipMemcpyHostToDevice, stream));
-      // host_buf is pageable and reused by the next call: wait for the copy
-      // (test transport, latency irrelevant)
-      HIP_OK(hipStreamSynchronize(stream));
-      return;
-    }
-    NCCL_OK(ncclAllReduce(d, d, count, ncclDouble, op, comm, stream));
-  }
-  // host values (set_problem structure, bench timing); one device scratch
-  // buffer, grown on demand and kept for the context's lifetime
-  double* hv_scratch = nullptr;
-  size_t hv_cap = 0;
-  void allreduce_host_values(double* v, size_t count, int op) {
-    if (!has_comm() || count == 0) return;
-    if (count > hv_cap) {
-      if (hv_scratch) { (void)hipStreamSynchronize(stream); (void)hipFree(hv_scratch); hv_scratch = nullptr; hv_cap = 0; }
-      HIP_OK(hipMalloc(&hv_scratch, sizeof(double) * count));
-      hv_cap = count;
-    }
-    HIP_OK(hipMemcpyAsync(hv_scratch, v, sizeof(double) * count, hipMemcpyHostToDevice, stream));
-    allreduce(hv_scratch, count, op == 1 ? ncclMax : ncclSum);
-    HIP_OK(hipMemcpyAsync(v, hv_scratch, sizeof(double) * count, hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-  }
-  // The scalar record to the host: a one-workgroup kernel stores it into the
-  // pinned, device-mapped record and then a sequence number (system-scope
-  // release), and the host spins on that number, instead of a D2H blit and
-  // a stream synchronisation (whose wake-up left ~20 us of idle device
-  // between an LM step and the next linearisation).  A device error or a
-  // missing number (bounded wait) falls back to the synchronisation, which
-  // reports it.  BA_SCAL_SPIN=0: the blit + synchronisation (A/B).
-  // publish_scalars() enqueues the record's transfer, wait_scalars() waits
-  // for it (work enqueued in between keeps the device busy meanwhile)
-  void read_scalars() {
-    publish_scalars();
-    wait_scalars();
-  }
-  bool scal_spin() const { return spin && d_hscal; }
-  // per-call switches (read at every ba_solve / ba_bench_iterations entry, so
-  // tests can A/B them in one process): BA_SPEC_LIN=0 turns the speculative
-  // linearisation off, BA_SCAL_SPIN=0 the spin-published scalar record
-  bool spec_lin = true, spin = true;
-  void read_env() {
-    const char* e = std::getenv("BA_SPEC_LIN");
-    spec_lin = !(e && e[0] == '0');
-    e = std::getenv("BA_SCAL_SPIN");
-    spin = !(e && e[0] == '0');
-  }
-  void publish_scalars() {
-    const size_t cnt = kNumSlots + kPcgState;
-    flush_norms();
-    if (!scal_spin()) {
-      if (pend_sum | pend_max) bahip::launch_reduce(W, pend_sum, pend_max, stream);
-      pend_sum = pend_max = 0;
-      HIP_OK(hipMemcpyAsync(h_scal, W.scal, sizeof(double) * cnt, hipMemcpyDeviceToHost, stream));
-      HIP_OK(hipEventRecord(ev[6], stream));
-      return;
-    }
-    // scalars still to be folded (pend_*: the step's and the deferred
-    // linearisation's, single rank): one launch folds and publishes them
-    if ((pend_sum | pend_max) && d_ticket) {
-      bahip::launch_reduce_publish(W, pend_sum, pend_max, d_hscal, (int)cnt, d_hseq, ++scal_seq, d_ticket, stream);
-      pend_sum = pend_max = 0;
-    } else {
-      if (pend_sum | pend_max) bahip::launch_reduce(W, pend_sum, pend_max, stream);
-      pend_sum = pend_max = 0;
-      bahip::launch_publish_scalars(W.scal, d_hscal, (int)cnt, d_hseq, ++scal_seq, stream);
-    }
-    HIP_OK(hipGetLastError());
-  }
-  void wait_scalars() {
-    if (!scal_spin()) {
-      HIP_OK(hipEventSynchronize(ev[6]));
-      return;
-    }
-    const unsigned seq = scal_seq;
-    const double t0 = now_s();
-    for (unsigned it = 1;; ++it) {
-      if (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) == seq) return;
-      if ((it & 1023u) == 0 && now_s() - t0 > 2.0) break;
-    }
-    HIP_OK(hipStreamSynchronize(stream));   // (raises a device error)
-    if (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != seq)
-      throw BaError{BA_ERR_DEVICE, "scalar record: sequence number not received"};
-  }
-};
-
-namespace {
-
-// Room for `bytes`.  Growing waits for the stream before it frees the old
-// buffer; a failed allocation leaves the arena empty and no sticky error, so
-// the context stays usable.
-void StagingArena::reserve(ba_ctx* ctx, size_t bytes, const std::string& fn) {
-  if (bytes <= cap) return;
-  if (dev) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(dev); }
-  dev = nullptr; cap = 0;
-  const hipError_t e = hipMalloc(&dev, bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    dev = nullptr;
-    throw BaError{e == hipErrorOutOfMemory ? BA_ERR_OUT_OF_MEMORY : BA_ERR_DEVICE,
-                  fn + "scratch of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e)};
-  }
-  cap = bytes;
-}
-
-template <class T> T* at(char* base, size_t off) { return reinterpret_cast<T*>(base + off); }
-// a section of a staging buffer's host copy
-void stage(std::vector<char>& h, size_t off, const void* src, size_t nb) { if (nb) std::memcpy(h.data() + off, src, nb); }
-
-ba_options options_or_default(const ba_options* opt) {
-  ba_options o;
-  if (opt) o = *opt; else ba_default_options(&o);
-  return o;
-}
-PoseOpts pose_opts(const ba_options& o) {
-  return PoseOpts{o.max_num_iterations, o.max_num_consecutive_invalid_steps, o.jacobi_scaling,
-                  o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance, o.initial_trust_region_radius,
-                  o.max_trust_region_radius, o.min_trust_region_radius, o.min_relative_decrease, o.min_lm_diagonal,
-                  o.max_lm_diagonal};
-}
-// the *_times getters: up to n values into ms, returns how many there are
-int copy_times(const std::vector<double>& t, double* ms, int n) {
-  const int m = (int)t.size();
-  for (int i = 0; i < std::min(n, m) && ms; ++i) ms[i] = t[i];
-  return m;
-}
 
 // ---------------------------------------------------------------------------
 // structure build
@@ -2035,23 +1706,6 @@ void debug_factor(ba_ctx* ctx, const double* S_in, const double* rhs_in, double*
 // ============================================================================
 // extern "C" ABI
 // ============================================================================
-template <typename F>
-static int guarded(ba_ctx* ctx, F&& f) {
-  try {
-    f();
-    return BA_OK;
-  } catch (const BaError& e) {
-    if (ctx) ctx->err = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    if (ctx) ctx->err = e.what();
-    return BA_ERR_DEVICE;
-  } catch (...) {
-    if (ctx) ctx->err = "unknown error";
-    return BA_ERR_DEVICE;
-  }
-}
-
 extern "C" {
 
 int ba_abi_version(void) { return BA_ABI_VERSION; }
@@ -2099,12 +1753,9 @@ int ba_destroy(ba_ctx* ctx) {
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
-  for (StagingArena* a : {&ctx->pose, &ctx->win, &ctx->tri, &ctx->pnp, &ctx->tv, &ctx->match, &ctx->mp, &ctx->mg, &ctx->icp}) (void)hipFree(a->dev);
-  for (char* b : ctx->graph.buf) (void)hipFree(b);
-  for (hipEvent_t e : ctx->match_ev) if (e) (void)hipEventDestroy(e);
   if (ctx->hv_scratch) (void)hipFree(ctx->hv_scratch);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;   // (the staging arenas and the list buffers free their device memory here)
   return BA_OK;
 }
 
@@ -2255,1248 +1906,6 @@ int ba_linearize(ba_ctx* ctx, double* r, double* J, double* cost) {
         }
     }
     if (cost) *cost = L.cost;
-  });
-}
-
-int ba_prune(ba_ctx* ctx, const ba_prune_problem* p, uint8_t* result) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    if (!p || p->n_cams < 0 || p->n_obs < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_prune: bad sizes"};
-    const int nc = p->n_cams, no = p->n_obs;
-    if (no == 0) return;
-    if (!p->extr || !p->cam_center || !p->K || !p->obs_cam || !p->obs_X || !p->obs_uv || !p->obs_inv_sigma ||
-        !p->obs_dist || !result)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_prune: null array"};
-    for (int o = 0; o < no; ++o)
-      if (p->obs_cam[o] < 0 || p->obs_cam[o] >= nc)
-        throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_prune: obs_cam[" + std::to_string(o) + "] out of range"};
-    HIP_OK(hipSetDevice(ctx->device));
-    // one staging buffer: cameras (16 + 3 + 9 floats) then pairs (1 int + 3 + 2 + 1 + 2 floats + 1 byte)
-    SectionLayout L(1);   // (packed: every section is a multiple of its element size)
-    const size_t NC = nc, NO = no;
-    const size_t o_extr = L.add(sizeof(float) * 16 * NC), o_ctr = L.add(sizeof(float) * 3 * NC),
-                 o_K = L.add(sizeof(float) * 9 * NC), o_X = L.add(sizeof(float) * 3 * NO),
-                 o_uv = L.add(sizeof(float) * 2 * NO), o_sig = L.add(sizeof(float) * NO),
-                 o_dist = L.add(sizeof(float) * 2 * NO), o_cam = L.add(sizeof(int) * NO);
-    L.end_inputs();
-    const size_t o_res = L.add(NO);
-    char* d = nullptr;
-    HIP_OK(hipMalloc(&d, L.total));
-    DevFree guard{d};
-    std::vector<char> h(L.in_b);
-    stage(h, o_extr, p->extr, sizeof(float) * 16 * NC);
-    stage(h, o_ctr, p->cam_center, sizeof(float) * 3 * NC);
-    stage(h, o_K, p->K, sizeof(float) * 9 * NC);
-    stage(h, o_X, p->obs_X, sizeof(float) * 3 * NO);
-    stage(h, o_uv, p->obs_uv, sizeof(float) * 2 * NO);
-    stage(h, o_sig, p->obs_inv_sigma, sizeof(float) * NO);
-    stage(h, o_dist, p->obs_dist, sizeof(float) * 2 * NO);
-    stage(h, o_cam, p->obs_cam, sizeof(int) * NO);
-    HIP_OK(hipMemcpyAsync(d, h.data(), L.in_b, hipMemcpyHostToDevice, ctx->stream));
-    launch_prune(no, at<const float>(d, o_extr), at<const float>(d, o_ctr), at<const float>(d, o_K),
-                 at<const int>(d, o_cam), at<const float>(d, o_X), at<const float>(d, o_uv),
-                 at<const float>(d, o_sig), at<const float>(d, o_dist), at<uint8_t>(d, o_res), ctx->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(result, d + o_res, NO, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-  });
-}
-
-int ba_solve_pose_batch(ba_ctx* ctx, const ba_pose_batch* b, const ba_options* opt, double* cams_out,
-                        ba_summary* summaries) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    if (!b || b->n_problems < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_solve_pose_batch: bad batch"};
-    const int n = b->n_problems;
-    if (n == 0) return;
-    if (!b->obs_offset || !b->cams || !b->K || !cams_out)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_solve_pose_batch: null array"};
-    const std::string fn = "ba_solve_pose_batch: ";
-    check_offsets(fn.c_str(), "obs_offset", b->obs_offset, n);
-    const size_t N = n, NO = b->obs_offset[n];
-    if (NO > 0 && (!b->pts || !b->obs_uv)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null array"};
-    const PoseOpts po = pose_opts(options_or_default(opt));
-    const double t0 = now_s();
-    HIP_OK(hipSetDevice(ctx->device));
-    // one staging buffer, 16-B aligned sections: inputs (uploaded), then outputs
-    SectionLayout L(16);
-    const size_t o_off = L.add(sizeof(int) * (N + 1)), o_cam = L.add(sizeof(double) * 6 * N),
-                 o_K = L.add(sizeof(float) * 9 * N), o_X = L.add(sizeof(double) * 3 * NO),
-                 o_uv = L.add(sizeof(float) * 2 * NO);
-    L.end_inputs();
-    const size_t o_out = L.add(sizeof(double) * 6 * N), o_sum = L.add(sizeof(double) * 8 * N);
-    L.end_outputs();
-    ctx->pose.reserve(ctx, L.total, fn);
-    std::vector<char>& h = ctx->pose.host;
-    h.assign(L.total, 0);
-    stage(h, o_off, b->obs_offset, sizeof(int) * (N + 1));
-    stage(h, o_cam, b->cams, sizeof(double) * 6 * N);
-    stage(h, o_K, b->K, sizeof(float) * 9 * N);
-    stage(h, o_X, b->pts, sizeof(double) * 3 * NO);
-    stage(h, o_uv, b->obs_uv, sizeof(float) * 2 * NO);
-    char* d = ctx->pose.dev;
-    HIP_OK(hipMemcpyAsync(d, h.data(), L.in_b, hipMemcpyHostToDevice, ctx->stream));
-    launch_pose_batch(n, at<const int>(d, o_off), at<const double>(d, o_cam), at<const float>(d, o_K),
-                      at<const double>(d, o_X), at<const float2>(d, o_uv), b->huber_a, po, at<double>(d, o_out),
-                      at<double>(d, o_sum), ctx->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(h.data() + L.in_b, d + L.in_b, L.io_b - L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(cams_out, h.data() + o_out, sizeof(double) * 6 * N);
-    if (summaries) {
-      const double wall = now_s() - t0;
-      for (size_t i = 0; i < N; ++i) summaries[i] = unpack_summary(at<const double>(h.data(), o_sum) + 8 * i, wall, false);
-    }
-  });
-}
-
-// ---------------------------------------------------------------------------
-// ba_solve_window_batch: host side.  The structure of every problem
-// (pack_window_structure, host/ba_batch_pack.hpp), one upload, one launch
-// (ba_window.hip), one download.
-// ---------------------------------------------------------------------------
-int ba_solve_window_batch(ba_ctx* ctx, const ba_window_batch* b, const ba_options* opt, double* cams_out,
-                          double* pts_out, ba_summary* summaries) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_solve_window_batch: ";
-    if (!b || b->n_problems < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "bad batch"};
-    const ba_options o = options_or_default(opt);
-    if (o.linear_solver != BA_DENSE_SCHUR) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "linear_solver must be BA_DENSE_SCHUR"};
-    if (o.precision != BA_FP64) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "precision must be BA_FP64"};
-    const double t0 = now_s();
-    const WindowPack w = pack_window_structure(*b);
-    const int n = b->n_problems;
-    const size_t NC = w.cam_vc.size(), NP = w.pt_var.size(), NO = w.obs_cam.size(), NV = w.NV;
-    if ((NC && (!b->cams || !b->K || !cams_out)) || (NP && (!b->pts || !pts_out)))
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null array"};
-    if (n == 0) {
-      ctx->win_log.clear();
-      ctx->win_log_n.clear();
-      return;
-    }
-    // the launch's dynamic LDS: the largest over the problems (not monotone in nvc)
-    size_t lds = 0;
-    for (const WinProb& q : w.prob) lds = std::max(lds, window_lds_bytes(q.nvc));
-    // ---- one buffer: inputs (uploaded) | outputs (downloaded) | scratch
-    const size_t log_cap = (size_t)std::max(o.max_num_iterations, 0) + 1;
-    if (log_cap > (size_t(1) << 40) / (sizeof(ba_iteration) * (size_t)n))
-      throw BaError{BA_ERR_OUT_OF_MEMORY, fn + "the iteration logs do not fit (max_num_iterations x n_problems)"};
-    SectionLayout L(256);
-    const size_t o_prob = L.add(sizeof(WinProb) * n), o_cams = L.add(sizeof(double) * 6 * NC),
-                 o_pts = L.add(sizeof(double) * 3 * NP), o_K = L.add(sizeof(float) * 9 * NC),
-                 o_extr = L.add(sizeof(float) * 16 * NC), o_vc = L.add(sizeof(int) * NC), o_pv = L.add(NP),
-                 o_poff = L.add(sizeof(int) * (NP + n)), o_oc = L.add(sizeof(int) * NO),
-                 o_slot = L.add(sizeof(int) * NO), o_uv = L.add(sizeof(float) * 2 * NO),
-                 o_coff = L.add(sizeof(int) * w.cam_off.size()), o_cobs = L.add(sizeof(int) * w.cam_obs.size());
-    L.end_inputs();
-    const size_t o_co = L.add(sizeof(double) * 6 * NC), o_po = L.add(sizeof(double) * 3 * NP),
-                 o_sum = L.add(sizeof(double) * 8 * n), o_log = L.add(sizeof(ba_iteration) * log_cap * n);
-    L.end_outputs();
-    const size_t w_pts = L.add(sizeof(double) * 6 * NP), w_ctab = L.add(sizeof(double) * 2 * kWinTbl * NC),
-                 w_vrec = L.add(sizeof(double) * kWinVRec * NC), w_JR = L.add(sizeof(double) * 2 * kWinJR * NO),
-                 w_Hp = L.add(sizeof(double) * 18 * NP), w_sp = L.add(sizeof(double) * 3 * NP),
-                 w_prec = L.add(sizeof(double) * 9 * NP), w_W = L.add(sizeof(double) * 18 * NO),
-                 w_hc = L.add(sizeof(double) * 54 * NV);
-    HIP_OK(hipSetDevice(ctx->device));
-    ctx->win.reserve(ctx, L.total, fn);
-    std::vector<char>& h = ctx->win.host;
-    h.resize(L.io_b);
-    stage(h, o_prob, w.prob.data(), sizeof(WinProb) * n);
-    stage(h, o_cams, b->cams, sizeof(double) * 6 * NC);
-    stage(h, o_pts, b->pts, sizeof(double) * 3 * NP);
-    stage(h, o_K, b->K, sizeof(float) * 9 * NC);
-    if (b->cam_fixed_extr) stage(h, o_extr, b->cam_fixed_extr, sizeof(float) * 16 * NC);
-    else std::memset(h.data() + o_extr, 0, sizeof(float) * 16 * NC);
-    stage(h, o_vc, w.cam_vc.data(), sizeof(int) * NC);
-    stage(h, o_pv, w.pt_var.data(), NP);
-    stage(h, o_poff, w.pt_off.data(), sizeof(int) * (NP + n));
-    stage(h, o_oc, w.obs_cam.data(), sizeof(int) * NO);
-    stage(h, o_slot, w.obs_slot.data(), sizeof(int) * NO);
-    stage(h, o_uv, w.uv.data(), sizeof(float) * 2 * NO);
-    stage(h, o_coff, w.cam_off.data(), sizeof(int) * w.cam_off.size());
-    stage(h, o_cobs, w.cam_obs.data(), sizeof(int) * w.cam_obs.size());
-    char* d = ctx->win.dev;
-    HIP_OK(hipMemcpyAsync(d, h.data(), L.in_b, hipMemcpyHostToDevice, ctx->stream));
-    WinArgs A{};
-    A.prob = at<const WinProb>(d, o_prob);
-    A.NC = NC; A.NP = NP; A.NO = NO; A.NV = NV;
-    A.log_cap = (int)std::min<size_t>(log_cap, 0x7fffffff);
-    A.huber_a = b->huber_a;
-    A.cams_in = at<double>(d, o_cams); A.pts_in = at<double>(d, o_pts);
-    A.K = at<const float>(d, o_K); A.extr = at<const float>(d, o_extr);
-    A.cam_vc = at<const int>(d, o_vc); A.pt_var = at<const uint8_t>(d, o_pv);
-    A.pt_off = at<const int>(d, o_poff); A.obs_cam = at<const int>(d, o_oc); A.obs_slot = at<const int>(d, o_slot);
-    A.uv = at<const float2>(d, o_uv);
-    A.cam_off = at<const int>(d, o_coff); A.cam_obs = at<const int>(d, o_cobs);
-    A.pts = at<double>(d, w_pts); A.ctab = at<double>(d, w_ctab); A.vrec = at<double>(d, w_vrec);
-    A.JR = at<double>(d, w_JR); A.Hp = at<double>(d, w_Hp); A.scale_p = at<double>(d, w_sp);
-    A.prec = at<double>(d, w_prec); A.Wb = at<double>(d, w_W); A.hc = at<double>(d, w_hc);
-    A.cams_out = at<double>(d, o_co); A.pts_out = at<double>(d, o_po); A.summ = at<double>(d, o_sum); A.log = d + o_log;
-    const PoseOpts po = pose_opts(o);
-    const double t_prep = now_s() - t0;
-    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HIP_OK((hipError_t)launch_window_batch(n, A, po, lds, ctx->stream));
-    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
-    HIP_OK(hipMemcpyAsync(h.data() + L.in_b, d + L.in_b, L.io_b - L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    float kernel_ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
-    if (NC) std::memcpy(cams_out, h.data() + o_co, sizeof(double) * 6 * NC);
-    if (NP) std::memcpy(pts_out, h.data() + o_po, sizeof(double) * 3 * NP);
-    const double* sm = at<const double>(h.data(), o_sum);
-    ctx->win_log_cap = A.log_cap;
-    ctx->win_log_n.resize(n);
-    const ba_iteration* lg = at<const ba_iteration>(h.data(), o_log);
-    ctx->win_log.assign(lg, lg + log_cap * n);
-    const double wall = now_s() - t0;
-    ctx->win_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * wall};
-    for (int i = 0; i < n; ++i) {
-      ctx->win_log_n[i] = (int)sm[8 * i + 6];
-      if (summaries) summaries[i] = unpack_summary(sm + 8 * i, wall, true);
-    }
-  });
-}
-
-int ba_get_window_iteration_log(ba_ctx* ctx, int problem, ba_iteration* out, int n) {
-  if (!ctx || problem < 0 || problem >= (int)ctx->win_log_n.size()) return -BA_ERR_INVALID_ARGUMENT;
-  const int avail = ctx->win_log_n[problem];
-  const int k = std::min(n, avail);
-  if (out && k > 0)
-    std::memcpy(out, ctx->win_log.data() + (size_t)problem * ctx->win_log_cap, sizeof(ba_iteration) * k);
-  return avail;
-}
-
-int ba_window_times(ba_ctx* ctx, double* ms, int n) {
-  return ctx ? copy_times(ctx->win_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
-}
-
-// ---------------------------------------------------------------------------
-// ba_triangulate: host side.  Validate everything the kernel indexes with,
-// one staging upload, the prologue + one launch (ba_triangulate.hip), one
-// download.  The context's current problem is not touched.
-// ---------------------------------------------------------------------------
-void ba_triangulate_defaults(ba_tri_options* opt) {
-  if (!opt) return;
-  opt->init = BA_TRI_INIT_DLT;
-  opt->refine = 0;
-  opt->min_views = 2;
-  opt->checks = BA_TRI_CHECK_CHEIRALITY | BA_TRI_CHECK_CHI2 | BA_TRI_CHECK_SCALE;
-  opt->behind_rule = 0;
-  opt->reserved = 0;
-}
-
-int ba_triangulate(ba_ctx* ctx, const ba_tri_batch* b, const ba_tri_options* topt, const ba_options* opt,
-                   double* pts_out, uint8_t* status, ba_summary* summaries) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_triangulate: ";
-    if (!b || b->n_pts < 0 || b->n_cams < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "bad batch"};
-    ba_tri_options t;
-    if (topt) t = *topt; else ba_triangulate_defaults(&t);
-    if (t.init != BA_TRI_INIT_DLT && t.init != BA_TRI_INIT_GIVEN)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "unknown init " + std::to_string(t.init)};
-    if (t.refine != 0 && t.refine != 1) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "unknown refine " + std::to_string(t.refine)};
-    if (t.behind_rule != 0 && t.behind_rule != 1)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "unknown behind_rule " + std::to_string(t.behind_rule)};
-    const int all_checks = BA_TRI_CHECK_CHEIRALITY | BA_TRI_CHECK_CHI2 | BA_TRI_CHECK_SCALE;
-    if (t.checks & ~all_checks) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "unknown checks bits " + std::to_string(t.checks)};
-    if (t.min_views < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "min_views " + std::to_string(t.min_views) + " is negative"};
-    ba_options o = options_or_default(opt);
-    if (t.refine) {
-      if (o.linear_solver != BA_DENSE_SCHUR) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "linear_solver must be BA_DENSE_SCHUR"};
-      if (o.precision != BA_FP64) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "precision must be BA_FP64"};
-    }
-    const int np = b->n_pts, nc = b->n_cams;
-    if (np == 0) return;
-    if (!b->obs_offset) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null obs_offset"};
-    if (!pts_out || !status) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    check_offsets(fn.c_str(), "obs_offset", b->obs_offset, np, "point");
-    const size_t no = (size_t)b->obs_offset[np];
-    if (no > 0 && (!b->obs_cam || !b->obs_uv)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null observation array"};
-    if (nc > 0 && (!b->extr || !b->K)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null camera array (extr, K)"};
-    if (nc > (int)(0x7fffffff / kTriRec)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "too many cameras"};
-    if (t.init == BA_TRI_INIT_GIVEN && !b->pts_init)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "init is BA_TRI_INIT_GIVEN but pts_init is null"};
-    if ((t.checks & BA_TRI_CHECK_SCALE) && no > 0 && !b->cam_center)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "the scale test is on but cam_center is null"};
-    for (size_t k = 0; k < no; ++k)
-      if (b->obs_cam[k] < 0 || b->obs_cam[k] >= nc)
-        throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "obs_cam[" + std::to_string(k) + "] = " + std::to_string(b->obs_cam[k]) +
-                                                   " out of range (" + std::to_string(nc) + " cameras)"};
-    const double t0 = now_s();
-    const bool given = t.init == BA_TRI_INIT_GIVEN, has_ctr = b->cam_center != nullptr, has_scale = b->obs_scale != nullptr;
-    // ---- one buffer: inputs (uploaded) | outputs (downloaded) | scratch
-    SectionLayout L(256);
-    const size_t o_extr = L.add(sizeof(float) * 16 * nc), o_ctr = L.add(has_ctr ? sizeof(float) * 3 * nc : 0),
-                 o_K = L.add(sizeof(float) * 9 * nc), o_off = L.add(sizeof(int) * ((size_t)np + 1)),
-                 o_oc = L.add(sizeof(int) * no), o_uv = L.add(sizeof(float) * 2 * no),
-                 o_sc = L.add(has_scale ? sizeof(float) * no : 0), o_init = L.add(given ? sizeof(double) * 3 * np : 0);
-    L.end_inputs();
-    const size_t o_pts = L.add(sizeof(double) * 3 * np), o_sum = L.add(sizeof(double) * 6 * np), o_st = L.add((size_t)np);
-    L.end_outputs();
-    const size_t w_rec = L.add(sizeof(double) * kTriRec * nc);
-    HIP_OK(hipSetDevice(ctx->device));
-    ctx->tri.reserve(ctx, L.total, fn);
-    std::vector<char>& h = ctx->tri.host;
-    h.resize(L.io_b);
-    stage(h, o_extr, b->extr, sizeof(float) * 16 * nc);
-    if (has_ctr) stage(h, o_ctr, b->cam_center, sizeof(float) * 3 * nc);
-    stage(h, o_K, b->K, sizeof(float) * 9 * nc);
-    stage(h, o_off, b->obs_offset, sizeof(int) * ((size_t)np + 1));
-    stage(h, o_oc, b->obs_cam, sizeof(int) * no);
-    stage(h, o_uv, b->obs_uv, sizeof(float) * 2 * no);
-    if (has_scale) stage(h, o_sc, b->obs_scale, sizeof(float) * no);
-    if (given) stage(h, o_init, b->pts_init, sizeof(double) * 3 * np);
-    char* d = ctx->tri.dev;
-    HIP_OK(hipMemcpyAsync(d, h.data(), L.in_b, hipMemcpyHostToDevice, ctx->stream));
-    TriArgs A{};
-    A.n_pts = np; A.n_cams = nc;
-    A.init_given = given; A.refine = t.refine; A.min_views = t.min_views; A.checks = t.checks;
-    A.behind_any = t.behind_rule;
-    A.huber_a = b->huber_a;
-    A.extr = at<const float>(d, o_extr); A.center = has_ctr ? at<const float>(d, o_ctr) : nullptr; A.K = at<const float>(d, o_K);
-    A.off = at<const int>(d, o_off); A.obs_cam = at<const int>(d, o_oc); A.uv = at<const float2>(d, o_uv);
-    A.scale = has_scale ? at<const float>(d, o_sc) : nullptr;
-    A.pts_init = given ? at<const double>(d, o_init) : nullptr;
-    A.rec = at<double>(d, w_rec);
-    A.pts_out = at<double>(d, o_pts); A.summ = at<double>(d, o_sum); A.status = at<uint8_t>(d, o_st);
-    const PoseOpts po = pose_opts(o);
-    const double t_prep = now_s() - t0;
-    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
-    launch_triangulate(A, po, ctx->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
-    HIP_OK(hipMemcpyAsync(h.data() + L.in_b, d + L.in_b, L.io_b - L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    float kernel_ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
-    std::memcpy(pts_out, h.data() + o_pts, sizeof(double) * 3 * np);
-    std::memcpy(status, h.data() + o_st, (size_t)np);
-    const double wall = now_s() - t0;
-    ctx->tri_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * wall};
-    if (summaries)
-      for (size_t i = 0; i < (size_t)np; ++i)
-        summaries[i] = unpack_summary(at<const double>(h.data(), o_sum) + 6 * i, wall, true);
-  });
-}
-
-int ba_triangulate_times(ba_ctx* ctx, double* ms, int n) {
-  return ctx ? copy_times(ctx->tri_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
-}
-
-// ---------------------------------------------------------------------------
-// ba_pnp_ransac: host side.  Validation and section layout are plain C++
-// (check_pnp, pnp_layout: host/ba_batch_pack.hpp); one staging upload, the
-// launches of ba_pnp.hip, one download.  The context's current problem is not
-// touched.
-// ---------------------------------------------------------------------------
-void ba_pnp_defaults(ba_pnp_options* opt) {
-  if (opt) pnp_defaults(*opt);
-}
-
-namespace {
-
-// the batch into the arena's host copy and onto the device; the kernel
-// arguments that name the inputs
-PnpArgs pnp_stage(ba_ctx* ctx, const ba_pose_batch* b, const ba_pnp_options& p, const PnpLayout& P, const std::string& fn) {
-  const size_t N = b->n_problems, NO = b->obs_offset[N];
-  HIP_OK(hipSetDevice(ctx->device));
-  ctx->pnp.reserve(ctx, P.L.total, fn);
-  std::vector<char>& h = ctx->pnp.host;
-  h.assign(P.L.io_b, 0);
-  stage(h, P.off, b->obs_offset, sizeof(int) * (N + 1));
-  if (b->cams) stage(h, P.prior, b->cams, sizeof(double) * 6 * N);
-  stage(h, P.K, b->K, sizeof(float) * 9 * N);
-  stage(h, P.X, b->pts, sizeof(double) * 3 * NO);
-  stage(h, P.uv, b->obs_uv, sizeof(float) * 2 * NO);
-  char* d = ctx->pnp.dev;
-  HIP_OK(hipMemcpyAsync(d, h.data(), P.L.in_b, hipMemcpyHostToDevice, ctx->stream));
-  PnpArgs A{};
-  A.n_prob = (int)N; A.H = p.max_hypotheses;
-  A.n_min = std::max(4, p.min_points); A.inl_min = std::max(4, p.min_inliers);
-  A.use_prior = p.use_prior; A.refine = p.refine;
-  A.seed = p.seed; A.thr2 = p.threshold_px * p.threshold_px; A.huber_a = b->huber_a;
-  A.off = at<const int>(d, P.off); A.prior = at<const double>(d, P.prior); A.K = at<const float>(d, P.K);
-  A.X = at<const double>(d, P.X); A.uv = at<const float2>(d, P.uv);
-  return A;
-}
-
-}  // namespace
-
-int ba_pnp_ransac(ba_ctx* ctx, const ba_pose_batch* b, const ba_pnp_options* popt, const ba_options* lm,
-                  double* cams_out, uint8_t* inlier, ba_pnp_result* results) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_pnp_ransac: ";
-    const ba_options o = options_or_default(lm);
-    const ba_pnp_options p = check_pnp(fn.c_str(), b, popt, &o);
-    const size_t N = b->n_problems;
-    if (N == 0) return;
-    const size_t NO = b->obs_offset[N];
-    if (!cams_out || (NO > 0 && !inlier)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const double t0 = now_s();
-    const int G = pnp_group(N, p.max_hypotheses);
-    const PnpLayout P = pnp_layout(N, NO, p.max_hypotheses, G, 0);
-    PnpArgs A = pnp_stage(ctx, b, p, P, fn);
-    A.G = G;
-    char* d = ctx->pnp.dev;
-    A.rec = at<double>(d, P.rec); A.cmask = at<uint8_t>(d, P.cmask); A.cnt = at<int>(d, P.cnt); A.coff = at<int>(d, P.coff);
-    A.Xc = at<double>(d, P.Xc); A.uvc = at<float2>(d, P.uvc);
-    A.cams_out = at<double>(d, P.cams_out); A.cam_ransac = at<double>(d, P.cam_ransac); A.summ = at<double>(d, P.summ);
-    A.res = at<int>(d, P.res); A.inlier = at<uint8_t>(d, P.inlier);
-    const double t_prep = now_s() - t0;
-    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
-    launch_pnp(A, pose_opts(o), ctx->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
-    std::vector<char>& h = ctx->pnp.host;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    float kernel_ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
-    std::memcpy(cams_out, h.data() + P.cams_out, sizeof(double) * 6 * N);
-    if (NO) std::memcpy(inlier, h.data() + P.inlier, NO);
-    const double wall = now_s() - t0;
-    ctx->pnp_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * wall};
-    if (results)
-      for (size_t i = 0; i < N; ++i) {
-        ba_pnp_result& r = results[i];
-        const int* ri = at<const int>(h.data(), P.res) + 4 * i;
-        r = ba_pnp_result{};
-        r.status = ri[0]; r.n_inliers = ri[1]; r.n_inliers_ransac = ri[2]; r.best_hypothesis = ri[3];
-        std::memcpy(r.cam_ransac, h.data() + P.cam_ransac + sizeof(double) * 6 * i, sizeof(double) * 6);
-        if (p.refine && (ri[0] == BA_PNP_OK || ri[0] == BA_PNP_REFINE_FAILED))
-          r.refine = unpack_summary(at<const double>(h.data(), P.summ) + 8 * i, wall, true);
-      }
-  });
-}
-
-int ba_pnp_times(ba_ctx* ctx, double* ms, int n) {
-  return ctx ? copy_times(ctx->pnp_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
-}
-
-int ba_pnp_hypotheses(ba_ctx* ctx, const ba_pose_batch* b, const ba_pnp_options* popt, int problem, int h0, int n,
-                      int32_t* sample, int32_t* n_sol, double* Rt, int32_t* count) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_pnp_hypotheses: ";
-    const ba_pnp_options p = check_pnp(fn.c_str(), b, popt, nullptr);
-    if (problem < 0 || problem >= b->n_problems)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "problem " + std::to_string(problem) + " out of range"};
-    if (h0 < 0 || n < 0 || (long long)h0 + n > p.max_hypotheses)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "hypotheses [" + std::to_string(h0) + ", " + std::to_string((long long)h0 + n) +
-                                                 ") outside max_hypotheses " + std::to_string(p.max_hypotheses)};
-    if (n == 0) return;
-    if (!sample || !n_sol || !Rt || !count) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const int nobs = b->obs_offset[problem + 1] - b->obs_offset[problem];
-    const bool prior_only = p.use_prior && h0 == 0 && n == 1;
-    if (nobs < 3 && !prior_only)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "problem " + std::to_string(problem) + " has fewer than 3 observations"};
-    const size_t N = b->n_problems, NO = b->obs_offset[N];
-    const PnpLayout P = pnp_layout(N, NO, p.max_hypotheses, 1, (size_t)n);
-    PnpArgs A = pnp_stage(ctx, b, p, P, fn);
-    A.G = 1;
-    char* d = ctx->pnp.dev;
-    const PnpDebug D{problem, h0, n, at<int>(d, P.dbg_sample), at<int>(d, P.dbg_nsol), at<double>(d, P.dbg_Rt),
-                     at<int>(d, P.dbg_count)};
-    launch_pnp_hypotheses(A, D, ctx->stream);
-    HIP_OK(hipGetLastError());
-    std::vector<char>& h = ctx->pnp.host;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(sample, h.data() + P.dbg_sample, sizeof(int32_t) * 3 * n);
-    std::memcpy(n_sol, h.data() + P.dbg_nsol, sizeof(int32_t) * n);
-    std::memcpy(Rt, h.data() + P.dbg_Rt, sizeof(double) * 48 * n);
-    std::memcpy(count, h.data() + P.dbg_count, sizeof(int32_t) * 4 * n);
-  });
-}
-
-// ---------------------------------------------------------------------------
-// ba_two_view_ransac: host side.  Validation and section layout are plain C++
-// (check_two_view, two_view_layout: host/ba_batch_pack.hpp); one staging
-// upload, the launches of ba_two_view.hip, one download.  The context's
-// current problem is not touched.
-// ---------------------------------------------------------------------------
-void ba_two_view_defaults(ba_two_view_options* opt) {
-  if (opt) two_view_defaults(*opt);
-}
-
-namespace {
-
-// the batch into the arena's host copy and onto the device; the kernel
-// arguments that name the inputs
-TvArgs two_view_stage(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_view_options& p, const TwoViewLayout& P,
-                      const std::string& fn) {
-  const size_t N = b->n_pairs, NM = b->match_offset[N];
-  HIP_OK(hipSetDevice(ctx->device));
-  ctx->tv.reserve(ctx, P.L.total, fn);
-  std::vector<char>& h = ctx->tv.host;
-  h.assign(P.L.io_b, 0);
-  stage(h, P.off, b->match_offset, sizeof(int) * (N + 1));
-  stage(h, P.K1, b->K1, sizeof(float) * 9 * N);
-  stage(h, P.K2, b->K2 ? b->K2 : b->K1, sizeof(float) * 9 * N);
-  two_view_pack_matches(b, NM, at<float>(h.data(), P.m));
-  char* d = ctx->tv.dev;
-  HIP_OK(hipMemcpyAsync(d, h.data(), P.L.in_b, hipMemcpyHostToDevice, ctx->stream));
-  TvArgs A{};
-  A.n_pair = (int)N; A.H = p.max_hypotheses;
-  A.n_min = std::max(8, p.min_points); A.inl_min = std::max(8, p.min_inliers); A.good_min = std::max(1, p.min_good);
-  A.model = p.model; A.G = 1;
-  A.seed = p.seed; A.thr2 = p.threshold_px * p.threshold_px; A.h_ratio = p.h_ratio;
-  A.off = at<const int>(d, P.off); A.K1 = at<const float>(d, P.K1); A.K2 = at<const float>(d, P.K2);
-  A.m = at<const float4>(d, P.m);
-  A.models = at<double>(d, P.models); A.valid = at<int>(d, P.valid);
-  return A;
-}
-
-}  // namespace
-
-int ba_two_view_ransac(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_view_options* opt, uint8_t* inlier,
-                       ba_two_view_result* results) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_two_view_ransac: ";
-    const ba_two_view_options p = check_two_view(fn.c_str(), b, opt);
-    const size_t N = b->n_pairs;
-    if (N == 0) return;
-    const size_t NM = b->match_offset[N];
-    if (!results || (NM > 0 && !inlier)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const double t0 = now_s();
-    const int G = pnp_group(N, p.max_hypotheses);
-    const bool e5 = p.reserved == BA_TV_E_FIVE_POINT;
-    const int G5 = pnp_group(N, 10 * p.max_hypotheses);   // the vote of the five-point solutions runs over 10 H slots
-    const TwoViewLayout P = two_view_layout(N, NM, p.max_hypotheses, G, 0, e5, G5);
-    TvArgs A = two_view_stage(ctx, b, p, P, fn);
-    A.G = G;
-    char* d = ctx->tv.dev;
-    A.rec = at<unsigned long long>(d, P.rec); A.res = at<double>(d, P.res); A.inlier = at<uint8_t>(d, P.inlier);
-    if (e5) {
-      A.e5 = 1; A.G5 = G5;
-      A.models5 = at<double>(d, P.models5); A.nsol5 = at<int>(d, P.nsol5); A.rec5 = at<unsigned long long>(d, P.rec5);
-    }
-    const double t_prep = now_s() - t0;
-    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
-    launch_two_view(A, ctx->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
-    std::vector<char>& h = ctx->tv.host;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    float kernel_ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
-    if (NM) std::memcpy(inlier, h.data() + P.inlier, NM);
-    for (size_t i = 0; i < N; ++i) {
-      const double* r = at<const double>(h.data(), P.res) + (size_t)kTvRes * i;
-      ba_two_view_result& o = results[i];
-      o = ba_two_view_result{};
-      o.status = (int)r[0]; o.model = (int)r[1]; o.n_inliers = (int)r[2]; o.n_good = (int)r[3]; o.n_good_second = (int)r[4];
-      o.best_hypothesis_e = (int)r[5]; o.best_hypothesis_h = (int)r[6]; o.votes_e = (int)r[7]; o.votes_h = (int)r[8];
-      o.reserved = (int)r[38];
-      o.score_e = r[9]; o.score_h = r[10];
-      std::memcpy(o.E, r + 11, sizeof(double) * 9);
-      std::memcpy(o.H, r + 20, sizeof(double) * 9);
-      std::memcpy(o.cam, r + 29, sizeof(double) * 6);
-      std::memcpy(o.normal, r + 35, sizeof(double) * 3);
-    }
-    ctx->tv_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * (now_s() - t0)};
-  });
-}
-
-int ba_two_view_times(ba_ctx* ctx, double* ms, int n) {
-  return ctx ? copy_times(ctx->tv_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
-}
-
-int ba_two_view_hypotheses(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_view_options* opt, int pair, int h0, int n,
-                           int32_t* sample, double* E, double* H, int32_t* valid, int32_t* count) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_two_view_hypotheses: ";
-    const ba_two_view_options p = check_two_view(fn.c_str(), b, opt);
-    if (pair < 0 || pair >= b->n_pairs)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " out of range"};
-    if (h0 < 0 || n < 0 || (long long)h0 + n > p.max_hypotheses)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "hypotheses [" + std::to_string(h0) + ", " + std::to_string((long long)h0 + n) +
-                                                 ") outside max_hypotheses " + std::to_string(p.max_hypotheses)};
-    if (n == 0) return;
-    if (!sample || !E || !H || !valid || !count) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    if (b->match_offset[pair + 1] - b->match_offset[pair] < 8)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " has fewer than 8 matches"};
-    const size_t N = b->n_pairs, NM = b->match_offset[N];
-    const TwoViewLayout P = two_view_layout(N, NM, p.max_hypotheses, 1, (size_t)n);
-    TvArgs A = two_view_stage(ctx, b, p, P, fn);
-    A.n_min = 8;
-    char* d = ctx->tv.dev;
-    const TvDebug D{pair, h0, n, at<int>(d, P.dbg_sample), at<int>(d, P.dbg_count)};
-    launch_two_view_hypotheses(A, D, ctx->stream);
-    HIP_OK(hipGetLastError());
-    std::vector<char>& h = ctx->tv.host;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(sample, h.data() + P.dbg_sample, sizeof(int32_t) * 8 * n);
-    std::memcpy(valid, h.data() + P.valid, sizeof(int32_t) * 2 * n);
-    std::memcpy(count, h.data() + P.dbg_count, sizeof(int32_t) * 2 * n);
-    const double* m = at<const double>(h.data(), P.models);
-    for (int i = 0; i < n; ++i) {
-      std::memcpy(E + 9 * (size_t)i, m + 18 * (size_t)i, sizeof(double) * 9);
-      std::memcpy(H + 9 * (size_t)i, m + 18 * (size_t)i + 9, sizeof(double) * 9);
-    }
-  });
-}
-
-int ba_two_view_hypotheses_e5(ba_ctx* ctx, const ba_two_view_batch* b, const ba_two_view_options* opt, int pair, int h0, int n,
-                              int32_t* sample, int32_t* n_sol, double* E, int32_t* count) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_two_view_hypotheses_e5: ";
-    const ba_two_view_options p = check_two_view(fn.c_str(), b, opt);
-    if (pair < 0 || pair >= b->n_pairs)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " out of range"};
-    if (h0 < 0 || n < 0 || (long long)h0 + n > p.max_hypotheses)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "hypotheses [" + std::to_string(h0) + ", " + std::to_string((long long)h0 + n) +
-                                                 ") outside max_hypotheses " + std::to_string(p.max_hypotheses)};
-    if (n == 0) return;
-    if (!sample || !n_sol || !E || !count) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    if (b->match_offset[pair + 1] - b->match_offset[pair] < 8)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " has fewer than 8 matches"};
-    const size_t N = b->n_pairs, NM = b->match_offset[N];
-    const TwoViewLayout P = two_view_layout(N, NM, p.max_hypotheses, 1, (size_t)n, true);
-    TvArgs A = two_view_stage(ctx, b, p, P, fn);
-    A.n_min = 8;
-    char* d = ctx->tv.dev;
-    A.e5 = 1; A.G5 = 1;
-    A.models = nullptr; A.valid = nullptr;   // (the layout has no eight-point sections)
-    A.models5 = at<double>(d, P.models5); A.nsol5 = at<int>(d, P.nsol5);
-    TvDebug D{pair, h0, n, at<int>(d, P.dbg_sample), nullptr, at<int>(d, P.dbg_count5)};
-    launch_two_view_hypotheses_e5(A, D, ctx->stream);
-    HIP_OK(hipGetLastError());
-    std::vector<char>& h = ctx->tv.host;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(sample, h.data() + P.dbg_sample, sizeof(int32_t) * 8 * n);
-    std::memcpy(n_sol, h.data() + P.nsol5, sizeof(int32_t) * n);
-    std::memcpy(count, h.data() + P.dbg_count5, sizeof(int32_t) * 10 * n);
-    const double* m = at<const double>(h.data(), P.models5);   // [10][n][9] -> [n][10][9]
-    for (int i = 0; i < n; ++i)
-      for (int sidx = 0; sidx < 10; ++sidx)
-        std::memcpy(E + 9 * (10 * (size_t)i + sidx), m + 9 * ((size_t)sidx * n + i), sizeof(double) * 9);
-  });
-}
-
-// ---------------------------------------------------------------------------
-// ba_match_descriptors: host side.  Validation, the pair table and the section
-// layout are plain C++ (check_match, match_plan, match_layout:
-// host/ba_batch_pack.hpp); the tables go up through the staging copy and the
-// descriptors from the caller's array, then the launches of ba_match.hip and
-// one download.  The context's current problem is not touched.
-// ---------------------------------------------------------------------------
-void ba_match_defaults(ba_match_options* opt) {
-  if (opt) match_defaults(*opt);
-}
-
-namespace {
-
-// the batch (pairs [first, first + n) of it) into the arena's host copy and
-// onto the device; the kernel arguments
-MatchArgs match_stage(ba_ctx* ctx, const ba_match_batch* b, const ba_match_options& p, const MatchPlan& M,
-                      const MatchLayout& P, bool knn, const std::string& fn) {
-  const size_t rows = b->n_sets > 0 ? (size_t)b->set_offset[b->n_sets] : 0, dim = (size_t)b->dim;
-  const bool have_ref = b->row_ref != nullptr;
-  const size_t n_ref = have_ref ? (size_t)b->n_ref : 0;
-  HIP_OK(hipSetDevice(ctx->device));
-  ctx->match.reserve(ctx, P.L.total, fn);
-  // The descriptors are the bulk of the batch (125 MB for 256 pairs of 1000 x 1000) and the last input
-  // section: they go up from the caller's array, which the call outlives, not through the host copy.
-  std::vector<char>& h = ctx->match.host;
-  h.resize(P.L.io_b);
-  std::memset(h.data(), 0, P.desc);
-  stage(h, P.pair, M.pair.data(), sizeof(MatchPair) * M.pair.size());
-  if (have_ref) {
-    stage(h, P.row_ref, b->row_ref, sizeof(int32_t) * rows);
-    if (b->ref_desc) stage(h, P.ref, b->ref_desc, sizeof(float) * n_ref * dim);
-  }
-  char* d = ctx->match.dev;
-  if (P.desc) HIP_OK(hipMemcpyAsync(d, h.data(), P.desc, hipMemcpyHostToDevice, ctx->stream));
-  if (rows) HIP_OK(hipMemcpyAsync(d + P.desc, b->desc, sizeof(float) * rows * dim, hipMemcpyHostToDevice, ctx->stream));
-  MatchArgs A{};
-  A.n_pair = (int)M.pair.size(); A.dim = b->dim; A.rows = (int)rows; A.n_ref = (int)n_ref;
-  A.max_nq = M.max_nq; A.max_nt = M.max_nt; A.chunks = M.chunks; A.chunk_rows = M.chunk_rows;
-  A.select = knn ? 0 : 1; A.unique = p.unique; A.ratio = p.ratio; A.max_distance = p.max_distance;
-  A.pair = at<const MatchPair>(d, P.pair); A.desc = at<const float>(d, P.desc);
-  A.row_ref = have_ref ? at<const int>(d, P.row_ref) : nullptr; A.ref = at<const float>(d, P.ref);
-  A.norms = at<float>(d, P.norms); A.part = at<unsigned long long>(d, P.part); A.knn = at<ba_match_neighbors>(d, P.knn);
-  if (!knn) {
-    A.surv = at<uint8_t>(d, P.surv); A.win = at<unsigned long long>(d, P.win); A.hist = at<int>(d, P.hist);
-    A.cnt = at<int>(d, P.cnt); A.matches = at<ba_match>(d, P.matches);
-    if (M.NT) {   // no winner, no survivor yet
-      HIP_OK(hipMemsetAsync(A.win, 0xff, sizeof(uint64_t) * M.NT, ctx->stream));
-      HIP_OK(hipMemsetAsync(A.hist, 0, sizeof(int32_t) * M.NT, ctx->stream));
-    }
-  }
-  return A;
-}
-
-}  // namespace
-
-int ba_match_descriptors(ba_ctx* ctx, const ba_match_batch* b, const ba_match_options* opt, int32_t* match_offset,
-                         ba_match* matches) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_match_descriptors: ";
-    const ba_match_options p = check_match(fn.c_str(), b, opt);
-    if (!match_offset) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const size_t N = b->n_pairs;
-    match_offset[0] = 0;
-    if (N == 0) return;
-    const double t0 = now_s();
-    const MatchPlan M = match_plan(fn.c_str(), b, p.unique, 0, (int)N);
-    if (M.NM > 0 && !matches) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const size_t rows = (size_t)b->set_offset[b->n_sets];
-    const MatchLayout P = match_layout(M, rows, (size_t)b->n_ref, b->dim, b->row_ref != nullptr, false);
-    HIP_OK(hipSetDevice(ctx->device));
-    for (hipEvent_t& e : ctx->match_ev)
-      if (!e) HIP_OK(hipEventCreate(&e));
-    const MatchArgs A = match_stage(ctx, b, p, M, P, false, fn);
-    const double t_prep = now_s() - t0;
-    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
-    launch_match(A, ctx->stream, ctx->match_ev);
-    HIP_OK(hipGetLastError());
-    std::vector<char>& h = ctx->match.host;
-    char* d = ctx->match.dev;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    float ms[3] = {0.0f, 0.0f, 0.0f};
-    HIP_OK(hipEventElapsedTime(&ms[0], ctx->ev[0], ctx->match_ev[0]));
-    HIP_OK(hipEventElapsedTime(&ms[1], ctx->match_ev[0], ctx->match_ev[1]));
-    HIP_OK(hipEventElapsedTime(&ms[2], ctx->match_ev[1], ctx->match_ev[2]));
-    const int* cnt = at<const int>(h.data(), P.cnt);
-    const ba_match* rec = at<const ba_match>(h.data(), P.matches);
-    size_t o = 0;
-    for (size_t i = 0; i < N; ++i) {
-      const MatchPair& Q = M.pair[i];
-      const int c = std::min(std::max(cnt[i], 0), Q.cap);
-      if (c) std::memcpy(matches + o, rec + Q.moff, sizeof(ba_match) * (size_t)c);
-      o += (size_t)c;
-      match_offset[i + 1] = (int32_t)o;
-    }
-    ctx->match_ms = {1e3 * t_prep, (double)(ms[0] + ms[1] + ms[2]), 1e3 * (now_s() - t0), (double)ms[0], (double)ms[1],
-                     (double)ms[2]};
-  });
-}
-
-int ba_match_times(ba_ctx* ctx, double* ms, int n) {
-  return ctx ? copy_times(ctx->match_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
-}
-
-int ba_match_knn(ba_ctx* ctx, const ba_match_batch* b, int pair, ba_match_neighbors* out) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_match_knn: ";
-    const ba_match_options p = check_match(fn.c_str(), b, nullptr);
-    if (pair < 0 || pair >= b->n_pairs)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " out of range"};
-    const MatchPlan M = match_plan(fn.c_str(), b, 1, pair, 1);
-    if (M.NQ == 0) return;
-    if (!out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const size_t rows = (size_t)b->set_offset[b->n_sets];
-    const MatchLayout P = match_layout(M, rows, (size_t)b->n_ref, b->dim, b->row_ref != nullptr, true);
-    const MatchArgs A = match_stage(ctx, b, p, M, P, true, fn);
-    launch_match(A, ctx->stream, nullptr);
-    HIP_OK(hipGetLastError());
-    std::vector<char>& h = ctx->match.host;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, ctx->match.dev + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost,
-                          ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, h.data() + P.knn, sizeof(ba_match_neighbors) * M.NQ);
-  });
-}
-
-// ---------------------------------------------------------------------------
-// ba_map_points_update / ba_map_points_distances / ba_associate: host side.
-// Validation, the tier plan and the section layouts are plain C++
-// (check_map_points, map_points_plan, check_assoc: host/ba_batch_pack.hpp);
-// the tables go up through the staging copy and the descriptors from the
-// caller's array, then the launches of ba_map_points.hip and one download.
-// The context's current problem is not touched.
-// ---------------------------------------------------------------------------
-void ba_map_points_defaults(ba_map_point_options* opt) {
-  if (opt) map_points_defaults(*opt);
-}
-void ba_associate_defaults(ba_assoc_options* opt) {
-  if (opt) assoc_defaults(*opt);
-}
-
-namespace {
-
-MapPointsArgs map_points_stage(ba_ctx* ctx, const ba_map_point_batch* b, const ba_map_point_options& p,
-                               const MapPointsPlan& M, const MapPointsLayout& P, const std::string& fn) {
-  const size_t np = (size_t)b->n_pts, no = (size_t)b->obs_offset[np], dim = (size_t)b->dim;
-  HIP_OK(hipSetDevice(ctx->device));
-  ctx->mp.reserve(ctx, P.L.total, fn);
-  std::vector<char>& h = ctx->mp.host;
-  h.resize(P.L.io_b);
-  std::memset(h.data(), 0, P.desc);
-  stage(h, P.center, b->cam_center, sizeof(float) * 3 * (size_t)b->n_cams);
-  stage(h, P.pts, b->pts, sizeof(float) * 3 * np);
-  stage(h, P.off, b->obs_offset, sizeof(int32_t) * (np + 1));
-  stage(h, P.cam, b->obs_cam, sizeof(int32_t) * no);
-  stage(h, P.row, b->obs_row, sizeof(int32_t) * no);
-  if (b->obs_scale) stage(h, P.scale, b->obs_scale, sizeof(float) * no);
-  if (b->ref_obs) stage(h, P.ref, b->ref_obs, sizeof(int32_t) * np);
-  stage(h, P.order, M.order.data(), sizeof(int32_t) * M.order.size());
-  char* d = ctx->mp.dev;
-  HIP_OK(hipMemcpyAsync(d, h.data(), P.desc, hipMemcpyHostToDevice, ctx->stream));
-  // the descriptors are the bulk of the batch: they go up from the caller's array, which the call outlives
-  if (b->n_rows > 0 && no > 0)
-    HIP_OK(hipMemcpyAsync(d + P.desc, b->desc, sizeof(float) * (size_t)b->n_rows * dim, hipMemcpyHostToDevice, ctx->stream));
-  MapPointsArgs A{};
-  A.dim = b->dim; A.median_rule = p.median_rule; A.max_scale = p.max_scale;
-  for (int t = 0; t < 3; ++t) { A.first[t] = M.first[t]; A.count[t] = M.count[t]; }
-  A.center = at<const float>(d, P.center); A.pts = at<const float>(d, P.pts); A.obs_offset = at<const int>(d, P.off);
-  A.obs_cam = at<const int>(d, P.cam); A.obs_row = at<const int>(d, P.row);
-  A.obs_scale = b->obs_scale ? at<const float>(d, P.scale) : nullptr;
-  A.ref_obs = b->ref_obs ? at<const int>(d, P.ref) : nullptr;
-  A.desc = at<const float>(d, P.desc); A.order = at<const int>(d, P.order);
-  A.out = at<ba_map_point>(d, P.out); A.out_stride = 1;
-  return A;
-}
-
-}  // namespace
-
-int ba_map_points_update(ba_ctx* ctx, const ba_map_point_batch* b, const ba_map_point_options* opt, ba_map_point* out,
-                         float* desc_out) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_map_points_update: ";
-    const ba_map_point_options p = check_map_points(fn.c_str(), b, opt);
-    const size_t np = (size_t)b->n_pts, dim = (size_t)b->dim;
-    if (np == 0) return;
-    if (!out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const double t0 = now_s();
-    const MapPointsPlan M = map_points_plan(b, 0, b->n_pts);
-    const MapPointsLayout P = map_points_layout(b, np, desc_out != nullptr, 0);
-    MapPointsArgs A = map_points_stage(ctx, b, p, M, P, fn);
-    A.desc_out = desc_out ? at<float>(ctx->mp.dev, P.desc_out) : nullptr;
-    const double t_prep = now_s() - t0;
-    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
-    launch_map_points(A, ctx->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
-    std::vector<char>& h = ctx->mp.host;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, ctx->mp.dev + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    float kernel_ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&kernel_ms, ctx->ev[0], ctx->ev[1]));
-    std::memcpy(out, h.data() + P.out, sizeof(ba_map_point) * np);
-    if (desc_out) std::memcpy(desc_out, h.data() + P.desc_out, sizeof(float) * np * dim);
-    ctx->mp_ms = {1e3 * t_prep, (double)kernel_ms, 1e3 * (now_s() - t0)};
-  });
-}
-
-int ba_map_points_times(ba_ctx* ctx, double* ms, int n) {
-  return ctx ? copy_times(ctx->mp_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
-}
-
-int ba_map_points_distances(ba_ctx* ctx, const ba_map_point_batch* b, int point, float* D, float* m) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_map_points_distances: ";
-    ba_map_point_options p = check_map_points(fn.c_str(), b, nullptr);
-    if (point < 0 || point >= b->n_pts)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "point " + std::to_string(point) + " out of range"};
-    const size_t n = (size_t)(b->obs_offset[point + 1] - b->obs_offset[point]);
-    if (n == 0) return;
-    if (!D || !m) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const MapPointsPlan M = map_points_plan(b, point, 1);
-    const MapPointsLayout P = map_points_layout(b, 1, false, n);
-    MapPointsArgs A = map_points_stage(ctx, b, p, M, P, fn);
-    A.out_stride = 0;
-    A.dbg_D = at<float>(ctx->mp.dev, P.dbg_D); A.dbg_m = at<float>(ctx->mp.dev, P.dbg_m);
-    launch_map_points(A, ctx->stream);
-    HIP_OK(hipGetLastError());
-    std::vector<char>& h = ctx->mp.host;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, ctx->mp.dev + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(D, h.data() + P.dbg_D, sizeof(float) * n * n);
-    std::memcpy(m, h.data() + P.dbg_m, sizeof(float) * n);
-  });
-}
-
-int ba_associate(ba_ctx* ctx, const ba_assoc_batch* b, const ba_assoc_options* opt, ba_assoc_result* items,
-                 ba_fuse_result* fuse) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_associate: ";
-    const ba_assoc_options p = check_assoc(fn.c_str(), b, opt);
-    const size_t nc = (size_t)b->n_cams, np = (size_t)b->n_pts, ni = (size_t)b->n_items, nf = (size_t)b->n_fuse,
-                 dim = (size_t)b->dim;
-    if (ni + nf == 0) return;
-    if ((ni > 0 && !items) || (nf > 0 && !fuse)) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    if (ni + nf > 0x7fffffffull) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "more than 2^31 - 1 items and fuse pairs"};
-    const AssocLayout P = assoc_layout(b);
-    HIP_OK(hipSetDevice(ctx->device));
-    ctx->mp.reserve(ctx, P.L.total, fn);
-    std::vector<char>& h = ctx->mp.host;
-    h.resize(P.L.io_b);
-    std::memset(h.data(), 0, P.pt_desc);
-    auto put = [&](size_t off, const void* src, size_t nb) { if (src) stage(h, off, src, nb); };
-    put(P.extr, b->extr, sizeof(float) * 16 * nc); put(P.center, b->cam_center, sizeof(float) * 3 * nc);
-    put(P.K, b->K, sizeof(float) * 9 * nc); put(P.size, b->image_size, sizeof(int32_t) * 2 * nc);
-    put(P.pts, b->pts, sizeof(float) * 3 * np); put(P.dir, b->pt_view_dir, sizeof(float) * 3 * np);
-    put(P.dist, b->pt_dist, sizeof(float) * 2 * np); put(P.cam, b->item_cam, sizeof(int32_t) * ni);
-    put(P.pt, b->item_pt, sizeof(int32_t) * ni); put(P.uv, b->item_uv, sizeof(float) * 2 * ni);
-    put(P.scale, b->item_scale, sizeof(float) * ni); put(P.row, b->item_row, sizeof(int32_t) * ni);
-    put(P.cur, b->item_cur_row, sizeof(int32_t) * ni); put(P.fuse, b->fuse_pairs, sizeof(int32_t) * 2 * nf);
-    char* d = ctx->mp.dev;
-    if (P.pt_desc) HIP_OK(hipMemcpyAsync(d, h.data(), P.pt_desc, hipMemcpyHostToDevice, ctx->stream));
-    // the two descriptor tables go up from the caller's arrays, which the call outlives
-    if (np > 0 && b->pt_desc)
-      HIP_OK(hipMemcpyAsync(d + P.pt_desc, b->pt_desc, sizeof(float) * np * dim, hipMemcpyHostToDevice, ctx->stream));
-    if (b->n_rows > 0 && b->desc)
-      HIP_OK(hipMemcpyAsync(d + P.desc, b->desc, sizeof(float) * (size_t)b->n_rows * dim, hipMemcpyHostToDevice, ctx->stream));
-    AssocArgs A{};
-    A.dim = b->dim; A.n_items = b->n_items; A.n_fuse = b->n_fuse; A.opt = p;
-    A.extr = at<const float>(d, P.extr); A.center = at<const float>(d, P.center); A.K = at<const float>(d, P.K);
-    A.image_size = at<const int>(d, P.size); A.pts = at<const float>(d, P.pts); A.pt_view_dir = at<const float>(d, P.dir);
-    A.pt_dist = at<const float>(d, P.dist); A.pt_desc = at<const float>(d, P.pt_desc); A.desc = at<const float>(d, P.desc);
-    A.item_cam = at<const int>(d, P.cam); A.item_pt = at<const int>(d, P.pt); A.item_uv = at<const float>(d, P.uv);
-    A.item_scale = b->item_scale ? at<const float>(d, P.scale) : nullptr; A.item_row = at<const int>(d, P.row);
-    A.item_cur_row = b->item_cur_row ? at<const int>(d, P.cur) : nullptr; A.fuse_pairs = at<const int>(d, P.fuse);
-    A.items = at<ba_assoc_result>(d, P.items); A.fuse = at<ba_fuse_result>(d, P.fused);
-    launch_associate(A, ctx->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    if (ni) std::memcpy(items, h.data() + P.items, sizeof(ba_assoc_result) * ni);
-    if (nf) std::memcpy(fuse, h.data() + P.fused, sizeof(ba_fuse_result) * nf);
-  });
-}
-
-// ---------------------------------------------------------------------------
-// ba_map_graph / ba_map_graph_lists / ba_map_graph_weights: host side.
-// Validation, the frame-sorted view and the chunk size are plain C++
-// (check_map_table, map_graph_plan, map_graph_chunk: host/ba_batch_pack.hpp).
-// The table goes up from the caller's arrays once; the queries are served in
-// chunks under a fixed scratch budget: count launches, the chunk's records to
-// the host, a scan there, then the fill launches into the context's list
-// buffers.  The context's current problem is not touched.
-// ---------------------------------------------------------------------------
-void ba_map_graph_defaults(ba_graph_options* opt) {
-  if (opt) map_graph_defaults(*opt);
-}
-
-namespace {
-
-struct MapGraphLayout {
-  SectionLayout L{256};
-  size_t frame_id = 0, is_key = 0, pt_invalid = 0, pt_ref = 0, off = 0, frame = 0, octave = 0, outlier = 0, obs_pt = 0,
-         perm = 0, frame_off = 0, query = 0;
-  size_t rec = 0, status = 0;
-  size_t W = 0, lst_f = 0, lst_w = 0, best = 0, loc = 0, fix = 0, pre = 0, ptb = 0, offs = 0;
-};
-
-// Uploads the table, its frame-sorted view and the queries into ctx->mg and
-// returns the kernel arguments with the scratch of `chunk` queries.
-MapGraphArgs map_graph_stage(ba_ctx* ctx, const ba_map_table* t, const MapGraphPlan& M, const int32_t* query, int n_query,
-                             const ba_graph_options& p, int chunk, bool want_status, MapGraphLayout& P,
-                             const std::string& fn) {
-  const size_t nf = (size_t)t->n_frames, np = (size_t)t->n_pts, no = (size_t)t->n_obs, nq = (size_t)n_query,
-               fw = map_graph_words(t->n_frames), pw = p.build_windows ? map_graph_words(t->n_pts) : 0, nc = (size_t)chunk;
-  SectionLayout& L = P.L;
-  P.frame_id = L.add(4 * nf); P.is_key = L.add(t->frame_is_key ? nf : 0); P.pt_invalid = L.add(t->pt_invalid ? np : 0);
-  P.pt_ref = L.add(want_status ? 4 * np : 0); P.off = L.add(4 * (np + 1)); P.frame = L.add(4 * no);
-  P.octave = L.add(t->obs_octave ? 4 * no : 0); P.outlier = L.add(t->obs_outlier ? no : 0); P.obs_pt = L.add(4 * no);
-  P.perm = L.add(4 * no); P.frame_off = L.add(4 * (nf + 1)); P.query = L.add(4 * nq);
-  L.end_inputs();
-  P.rec = L.add(sizeof(ba_graph_frame) * nq); P.status = L.add(want_status ? np : 0);
-  L.end_outputs();
-  P.W = L.add(4 * nc * nf); P.lst_f = L.add(4 * nc * nf); P.lst_w = L.add(4 * nc * nf);
-  P.best = L.add(4 * nc * BA_WINDOW_MAX_CAMS); P.loc = L.add(4 * nc * fw); P.fix = L.add(4 * nc * fw);
-  P.pre = L.add(4 * nc * fw); P.ptb = L.add(4 * nc * pw); P.offs = L.add(sizeof(long long) * 4 * nc);
-  HIP_OK(hipSetDevice(ctx->device));
-  ctx->mg.reserve(ctx, L.total, fn);
-  char* d = ctx->mg.dev;
-  auto up = [&](size_t off, const void* src, size_t nb) {
-    if (src && nb) HIP_OK(hipMemcpyAsync(d + off, src, nb, hipMemcpyHostToDevice, ctx->stream));
-  };
-  up(P.frame_id, t->frame_id, 4 * nf); up(P.is_key, t->frame_is_key, nf); up(P.pt_invalid, t->pt_invalid, np);
-  if (want_status) up(P.pt_ref, t->pt_ref_frame, 4 * np);
-  up(P.off, t->obs_offset, 4 * (np + 1)); up(P.frame, t->obs_frame, 4 * no); up(P.octave, t->obs_octave, 4 * no);
-  up(P.outlier, t->obs_outlier, no); up(P.obs_pt, M.obs_pt.data(), 4 * no); up(P.perm, M.perm.data(), 4 * no);
-  up(P.frame_off, M.frame_off.data(), 4 * (nf + 1)); up(P.query, query, 4 * nq);
-  MapGraphArgs A{};
-  A.n_frames = t->n_frames; A.n_pts = t->n_pts; A.n_obs = t->n_obs;
-  A.th = p.th; A.n_best = p.n_best; A.order = p.order; A.build_windows = p.build_windows ? 1 : 0;
-  A.tile = map_graph_tile(p, t->n_frames); A.fraction = p.redundant_fraction;
-  A.frame_id = at<const int>(d, P.frame_id);
-  A.is_key = t->frame_is_key ? at<const uint8_t>(d, P.is_key) : nullptr;
-  A.pt_invalid = t->pt_invalid ? at<const uint8_t>(d, P.pt_invalid) : nullptr;
-  A.obs_offset = at<const int>(d, P.off); A.obs_frame = at<const int>(d, P.frame);
-  A.obs_octave = t->obs_octave ? at<const int>(d, P.octave) : nullptr;
-  A.obs_outlier = t->obs_outlier ? at<const uint8_t>(d, P.outlier) : nullptr;
-  A.obs_pt = at<const int>(d, P.obs_pt); A.perm = at<const int>(d, P.perm); A.frame_off = at<const int>(d, P.frame_off);
-  A.W = at<int>(d, P.W); A.lst_f = at<int>(d, P.lst_f); A.lst_w = at<int>(d, P.lst_w); A.best = at<int>(d, P.best);
-  A.locbits = at<unsigned>(d, P.loc); A.fixbits = at<unsigned>(d, P.fix); A.fixpre = at<int>(d, P.pre);
-  A.ptbits = at<unsigned>(d, P.ptb); A.off = at<const long long>(d, P.offs);
-  return A;
-}
-
-// Room for `need` elements in list array a, keeping the first `keep`
-void graph_lists_reserve(ba_ctx* ctx, int a, size_t need, size_t keep, const std::string& fn) {
-  GraphLists& G = ctx->graph;
-  if (need <= G.cap[a]) return;
-  const size_t cap = std::max(need, 2 * G.cap[a]), es = GraphLists::elem[a];
-  char* nb = nullptr;
-  const hipError_t e = hipMalloc(&nb, cap * es);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    throw BaError{e == hipErrorOutOfMemory ? BA_ERR_OUT_OF_MEMORY : BA_ERR_DEVICE,
-                  fn + "lists of " + std::to_string(cap * es) + " bytes: " + hipGetErrorString(e)};
-  }
-  if (G.buf[a]) {
-    if (keep) HIP_OK(hipMemcpyAsync(nb, G.buf[a], keep * es, hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(G.buf[a]);
-  }
-  G.buf[a] = nb; G.cap[a] = cap;
-}
-
-}  // namespace
-
-int ba_map_graph(ba_ctx* ctx, const ba_map_table* t, const int32_t* query, int n_query, const ba_graph_options* opt,
-                 ba_graph_frame* out, uint8_t* pt_status) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_map_graph: ";
-    const bool want_status = pt_status != nullptr;
-    const ba_graph_options p = check_map_table(fn.c_str(), t, query, n_query, opt, want_status);
-    if (n_query > 0 && !out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const double t0 = now_s();
-    GraphLists& G = ctx->graph;
-    G.valid = false;
-    for (size_t& l : G.len) l = 0;
-    const MapGraphPlan M = map_graph_plan(t);
-    const int chunk = map_graph_chunk(p, t, n_query);
-    MapGraphLayout P;
-    MapGraphArgs A = map_graph_stage(ctx, t, M, query, n_query, p, chunk, want_status, P, fn);
-    char* d = ctx->mg.dev;
-    const double t_prep = now_s() - t0;
-    double kernel_ms = 0.0;
-    auto timed = [&](auto&& launches) {
-      HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
-      launches();
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
-    };
-    auto add_time = [&] {
-      float ms = 0.0f;
-      HIP_OK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      kernel_ms += (double)ms;
-    };
-    std::vector<long long> offs;
-    for (int c0 = 0; c0 < n_query; c0 += chunk) {
-      const int n = std::min(chunk, n_query - c0);
-      A.query = at<const int>(d, P.query) + c0; A.rec = at<ba_graph_frame>(d, P.rec) + c0; A.n_chunk = n;
-      if (p.build_windows && P.offs > P.loc) HIP_OK(hipMemsetAsync(d + P.loc, 0, P.offs - P.loc, ctx->stream));
-      timed([&] { launch_map_graph_count(A, ctx->stream); });
-      HIP_OK(hipMemcpyAsync(out + c0, A.rec, sizeof(ba_graph_frame) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_OK(hipStreamSynchronize(ctx->stream));
-      add_time();
-      offs.resize(4 * (size_t)n);
-      size_t len[4] = {G.len[0], G.len[1], G.len[2], G.len[3]};
-      for (int i = 0; i < n; ++i) {
-        const ba_graph_frame& r = out[c0 + i];
-        for (int k = 0; k < 4; ++k) offs[4 * (size_t)i + k] = (long long)len[k];
-        len[0] += (size_t)r.degree; len[1] += (size_t)(r.n_local + r.n_fixed); len[2] += (size_t)r.n_win_pts;
-        len[3] += (size_t)r.n_win_obs;
-      }
-      for (int a = 0; a < GraphLists::kArrays; ++a)
-        graph_lists_reserve(ctx, a, len[GraphLists::kind[a]], G.len[GraphLists::kind[a]], fn);
-      for (int k = 0; k < 4; ++k) G.len[k] = len[k];
-      HIP_OK(hipMemcpyAsync(d + P.offs, offs.data(), sizeof(long long) * offs.size(), hipMemcpyHostToDevice, ctx->stream));
-      A.nbr_frame = at<int>(G.buf[0], 0); A.nbr_weight = at<int>(G.buf[1], 0); A.win_cam = at<int>(G.buf[2], 0);
-      A.win_cam_fixed = at<uint8_t>(G.buf[3], 0); A.win_pt = at<int>(G.buf[4], 0); A.win_obs = at<int>(G.buf[5], 0);
-      A.win_obs_cam = at<int>(G.buf[6], 0); A.win_obs_pt = at<int>(G.buf[7], 0);
-      timed([&] { launch_map_graph_fill(A, ctx->stream); });
-      HIP_OK(hipStreamSynchronize(ctx->stream));
-      add_time();
-    }
-    if (want_status && t->n_pts > 0) {
-      timed([&] {
-        launch_map_graph_status(A, at<const int>(d, P.pt_ref), p.current_frame_id, at<uint8_t>(d, P.status), ctx->stream);
-      });
-      HIP_OK(hipMemcpyAsync(pt_status, d + P.status, (size_t)t->n_pts, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_OK(hipStreamSynchronize(ctx->stream));
-      add_time();
-    }
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    G.valid = true;
-    ctx->mg_ms = {1e3 * t_prep, kernel_ms, 1e3 * (now_s() - t0)};
-  });
-}
-
-int ba_map_graph_lists(ba_ctx* ctx, const ba_graph_lists* out) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_map_graph_lists: ";
-    if (!out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output"};
-    const GraphLists& G = ctx->graph;
-    if (!G.valid) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "no ba_map_graph result on this context"};
-    void* dst[GraphLists::kArrays] = {out->nbr_frame, out->nbr_weight, out->win_cam, out->win_cam_fixed,
-                                      out->win_pt, out->win_obs, out->win_obs_cam, out->win_obs_pt};
-    HIP_OK(hipSetDevice(ctx->device));
-    for (int a = 0; a < GraphLists::kArrays; ++a) {
-      const size_t nb = G.len[GraphLists::kind[a]] * GraphLists::elem[a];
-      if (dst[a] && nb) HIP_OK(hipMemcpyAsync(dst[a], G.buf[a], nb, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-  });
-}
-
-int ba_map_graph_weights(ba_ctx* ctx, const ba_map_table* t, int frame, const ba_graph_options* opt, int32_t* W) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_map_graph_weights: ";
-    const int32_t q = frame;
-    ba_graph_options p = check_map_table(fn.c_str(), t, &q, 1, opt, false);
-    if (!W) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    p.build_windows = 0;
-    const MapGraphPlan M = map_graph_plan(t);
-    MapGraphLayout P;
-    MapGraphArgs A = map_graph_stage(ctx, t, M, &q, 1, p, 1, false, P, fn);
-    A.query = at<const int>(ctx->mg.dev, P.query); A.n_chunk = 1;
-    launch_map_graph_weights(A, ctx->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(W, A.W, sizeof(int32_t) * (size_t)t->n_frames, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-  });
-}
-
-int ba_map_graph_times(ba_ctx* ctx, double* ms, int n) {
-  return ctx ? copy_times(ctx->mg_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
-}
-
-// ---------------------------------------------------------------------------
-// ba_icp / ba_icp_nn: host side.  Validation, the grids, the source
-// permutations and the section layout are plain C++ (check_icp, icp_plan,
-// icp_layout: host/ba_batch_pack.hpp); the tables go up through the staging
-// copy and the clouds from the caller's array, then max_iterations + 1 rounds
-// of ba_icp.hip with no sync in between and one download.  The context's
-// current problem is not touched.
-// ---------------------------------------------------------------------------
-void ba_icp_defaults(ba_icp_options* opt) {
-  if (opt) icp_defaults(*opt);
-}
-
-namespace {
-
-// the batch (pairs [first, first + n) of it) into the arena's host copy and
-// onto the device; the kernel arguments
-IcpArgs icp_stage(ba_ctx* ctx, const ba_icp_batch* b, const ba_icp_options& p, const IcpPlan& M, const IcpLayout& P,
-                  int first, const std::string& fn) {
-  const size_t N = M.pair.size(), total = (size_t)b->set_offset[b->n_sets];
-  if (N > 65535) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "more than 65535 pairs"};
-  HIP_OK(hipSetDevice(ctx->device));
-  ctx->icp.reserve(ctx, P.L.total, fn);
-  std::vector<char>& h = ctx->icp.host;
-  h.resize(P.L.io_b);
-  std::memset(h.data(), 0, P.xyz);
-  stage(h, P.pair, M.pair.data(), sizeof(IcpPair) * N);
-  stage(h, P.grid, M.grid.data(), sizeof(IcpGrid) * M.grid.size());
-  stage(h, P.cell_start, M.cell_start.data(), sizeof(int32_t) * M.cell_start.size());
-  stage(h, P.sorted, M.sorted.data(), sizeof(IcpPt) * total);
-  stage(h, P.perm, M.perm.data(), sizeof(int32_t) * M.NS);
-  IcpState* st = at<IcpState>(h.data(), P.st);
-  for (size_t i = 0; i < N; ++i) {
-    const IcpPair& Q = M.pair[i];
-    IcpState& S = st[i];
-    for (int e = 0; e < 16; ++e) S.fin[e] = b->guess && e < 12 ? b->guess[16 * (first + i) + e] : (e % 5 == 0 ? 1.0f : 0.0f);
-    for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) S.M[3 * r + c] = S.fin[4 * r + c];
-      S.t[r] = S.fin[4 * r + 3];
-    }
-    S.state = BA_ICP_NOT_CONVERGED; S.converged = 0; S.iterations = 0; S.n_corr = 0;
-    S.apply_at = 0; S.n_flag = 0;
-    S.prev = DBL_MAX; S.fitness = DBL_MAX;
-    stage(h, P.cur + sizeof(float) * 3 * (size_t)Q.soff, b->xyz + 3 * (size_t)Q.s0, sizeof(float) * 3 * (size_t)Q.ns);
-  }
-  char* d = ctx->icp.dev;
-  HIP_OK(hipMemcpyAsync(d, h.data(), P.xyz, hipMemcpyHostToDevice, ctx->stream));
-  HIP_OK(hipMemcpyAsync(d + P.xyz, b->xyz, sizeof(float) * 3 * total, hipMemcpyHostToDevice, ctx->stream));
-  IcpArgs A{};
-  A.n_pair = (int)N; A.max_ns = M.max_ns; A.max_ring = kIcpMaxRing;
-  A.max_d2 = icp_gate(p.max_corr_dist); A.fit_range = p.fitness_max_range;
-  A.rules = IcpRules{p.max_iterations, p.min_correspondences, p.with_scale, p.mse_abs_eps, p.mse_rel_eps, p.transformation_eps};
-  A.pair = at<const IcpPair>(d, P.pair); A.grid = at<const IcpGrid>(d, P.grid);
-  A.cell_start = at<const int>(d, P.cell_start); A.sorted = at<const IcpPt>(d, P.sorted);
-  A.xyz = at<const float>(d, P.xyz); A.perm = at<const int>(d, P.perm);
-  A.st = at<IcpState>(d, P.st); A.cur = at<float>(d, P.cur); A.idx = at<int>(d, P.idx); A.d2 = at<float>(d, P.d2);
-  A.flag = at<int>(d, P.flag); A.part = at<double>(d, P.part); A.mse = at<double>(d, P.mse);
-  return A;
-}
-
-}  // namespace
-
-int ba_icp(ba_ctx* ctx, const ba_icp_batch* b, const ba_icp_options* opt, ba_icp_result* out, double* mse) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_icp: ";
-    const ba_icp_options p = check_icp(fn.c_str(), b, opt);
-    const size_t N = b->n_pairs;
-    if (N == 0) return;
-    if (!out) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const double t0 = now_s();
-    const IcpPlan M = icp_plan(fn.c_str(), b, p, 0, (int)N);
-    const IcpLayout P = icp_layout(M, (size_t)b->set_offset[b->n_sets], p.max_iterations, false);
-    const IcpArgs A = icp_stage(ctx, b, p, M, P, 0, fn);
-    HIP_OK(hipMemsetAsync(A.mse, 0, sizeof(double) * N * (size_t)p.max_iterations, ctx->stream));
-    const double t_prep = now_s() - t0;
-    HIP_OK(hipEventRecord(ctx->ev[0], ctx->stream));
-    for (int round = 0; round <= p.max_iterations; ++round) launch_icp_round(A, round, false, ctx->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ctx->ev[1], ctx->stream));
-    std::vector<char>& h = ctx->icp.host;
-    char* d = ctx->icp.dev;
-    HIP_OK(hipMemcpyAsync(h.data() + P.st, d + P.st, sizeof(IcpState) * N, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, d + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    float ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    const IcpState* st = at<const IcpState>(h.data(), P.st);
-    for (size_t i = 0; i < N; ++i) {
-      ba_icp_result& R = out[i];
-      std::memcpy(R.final, st[i].fin, sizeof R.final);
-      R.converged = st[i].converged; R.state = st[i].state; R.iterations = st[i].iterations; R.n_corr = st[i].n_corr;
-      R.fitness = st[i].fitness;
-    }
-    if (mse) std::memcpy(mse, h.data() + P.mse, sizeof(double) * N * (size_t)p.max_iterations);
-    ctx->icp_ms = {1e3 * t_prep, (double)ms, 1e3 * (now_s() - t0), (double)ms / (p.max_iterations + 1)};
-  });
-}
-
-int ba_icp_times(ba_ctx* ctx, double* ms, int n) {
-  return ctx ? copy_times(ctx->icp_ms, ms, n) : -BA_ERR_INVALID_ARGUMENT;
-}
-
-int ba_icp_nn(ba_ctx* ctx, const ba_icp_batch* b, int pair, const ba_icp_options* opt, int32_t* idx, float* d2) {
-  if (!ctx) return BA_ERR_INVALID_ARGUMENT;
-  return guarded(ctx, [&] {
-    const std::string fn = "ba_icp_nn: ";
-    const ba_icp_options p = check_icp(fn.c_str(), b, opt);
-    if (pair < 0 || pair >= b->n_pairs)
-      throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "pair " + std::to_string(pair) + " out of range"};
-    if (!idx || !d2) throw BaError{BA_ERR_INVALID_ARGUMENT, fn + "null output array"};
-    const IcpPlan M = icp_plan(fn.c_str(), b, p, pair, 1);
-    const IcpLayout P = icp_layout(M, (size_t)b->set_offset[b->n_sets], p.max_iterations, true);
-    const IcpArgs A = icp_stage(ctx, b, p, M, P, pair, fn);
-    launch_icp_round(A, 0, true, ctx->stream);
-    HIP_OK(hipGetLastError());
-    std::vector<char>& h = ctx->icp.host;
-    HIP_OK(hipMemcpyAsync(h.data() + P.L.in_b, ctx->icp.dev + P.L.in_b, P.L.io_b - P.L.in_b, hipMemcpyDeviceToHost,
-                          ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(idx, h.data() + P.idx, sizeof(int32_t) * M.NS);
-    std::memcpy(d2, h.data() + P.d2, sizeof(float) * M.NS);
   });
 }
 

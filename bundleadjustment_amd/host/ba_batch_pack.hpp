@@ -1,10 +1,16 @@
-// ba_batch_pack.hpp — host-only packing shared by the batch entry points of
-// ba_solver.hip: the error type, the section layout of a staging buffer, the
-// CSR-offset validation, the summary record, the validation and layout of
-// ba_pnp_ransac, ba_two_view_ransac, ba_match_descriptors, ba_map_points_update, ba_associate,
-// ba_map_graph (with its plain restatement) and ba_icp (with its grid plan), and the structure build of ba_solve_window_batch.  It indexes with caller-supplied arrays, so it is
-// plain C++17 without a HIP header and runs under ASan + UBSan
-// (tests/cpp/batch_pack.cpp, `make -C tests/cpp sanitize`).
+// ba_batch_pack.hpp — host-only packing of the batch entry points
+// (csrc/ba_batch.hip): the error type, the section layout of a staging buffer,
+// the CSR-offset validation, the summary record, and per entry point a
+// check_* (everything the kernels index with or branch on) and a *_layout (the
+// sections of its staging buffer):
+//   ba_prune, ba_solve_pose_batch, ba_triangulate,
+//   ba_pnp_ransac, ba_two_view_ransac and their inspection entries,
+//   ba_match_descriptors, ba_map_points_update, ba_associate,
+//   ba_map_graph (with its plain restatement), ba_icp (with its grid plan),
+//   ba_solve_window_batch (with its structure build).
+// It indexes with caller-supplied arrays, so it is plain C++17 without a HIP
+// header and runs under ASan + UBSan (tests/cpp/batch_pack.cpp,
+// `make -C tests/cpp sanitize`).
 #pragma once
 
 #include <algorithm>
@@ -53,6 +59,156 @@ inline ba_summary unpack_summary(const double* rec, double wall, bool split_time
   S.total_time_s = wall;
   if (split_times) S.linearize_time_s = S.solve_time_s = wall;
   return S;
+}
+
+// (static, here and below: a function of this header that the library's one
+// user does not inline would otherwise appear among its dynamic symbols)
+//
+// The index / hypothesis-range check of the inspection entries
+// (ba_pnp_hypotheses, ba_two_view_hypotheses, ba_two_view_hypotheses_e5):
+// `what` ("problem" / "pair") index in [0, count), hypotheses [h0, h0 + n)
+// inside max_hypotheses.
+static inline void check_hypothesis_range(const char* fn, const char* what, int index, int count, int h0, int n, int max_hypotheses) {
+  if (index < 0 || index >= count)
+    throw BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what + " " + std::to_string(index) + " out of range"};
+  if (h0 < 0 || n < 0 || (long long)h0 + n > max_hypotheses)
+    throw BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + "hypotheses [" + std::to_string(h0) + ", " +
+                                               std::to_string((long long)h0 + n) + ") outside max_hypotheses " +
+                                               std::to_string(max_hypotheses)};
+}
+
+// ---------------------------------------------------------------------------
+// ba_prune
+// ---------------------------------------------------------------------------
+static inline void check_prune(const ba_prune_problem* p, const uint8_t* result) {
+  if (!p || p->n_cams < 0 || p->n_obs < 0) throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_prune: bad sizes"};
+  if (p->n_obs == 0) return;
+  if (!p->extr || !p->cam_center || !p->K || !p->obs_cam || !p->obs_X || !p->obs_uv || !p->obs_inv_sigma ||
+      !p->obs_dist || !result)
+    throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_prune: null array"};
+  for (int o = 0; o < p->n_obs; ++o)
+    if (p->obs_cam[o] < 0 || p->obs_cam[o] >= p->n_cams)
+      throw BaError{BA_ERR_INVALID_ARGUMENT, "ba_prune: obs_cam[" + std::to_string(o) + "] out of range"};
+}
+
+// The staging buffer: cameras (16 + 3 + 9 floats) then pairs (1 int + 3 + 2 +
+// 1 + 2 floats) | one result byte per pair.  Packed: every section is a
+// multiple of its element size.
+struct PruneLayout {
+  SectionLayout L{1};
+  size_t extr = 0, ctr = 0, K = 0, X = 0, uv = 0, sig = 0, dist = 0, cam = 0;
+  size_t res = 0;
+};
+static inline PruneLayout prune_layout(size_t NC, size_t NO) {
+  PruneLayout P;
+  SectionLayout& L = P.L;
+  P.extr = L.add(sizeof(float) * 16 * NC); P.ctr = L.add(sizeof(float) * 3 * NC); P.K = L.add(sizeof(float) * 9 * NC);
+  P.X = L.add(sizeof(float) * 3 * NO); P.uv = L.add(sizeof(float) * 2 * NO); P.sig = L.add(sizeof(float) * NO);
+  P.dist = L.add(sizeof(float) * 2 * NO); P.cam = L.add(sizeof(int32_t) * NO);
+  L.end_inputs();
+  P.res = L.add(NO);
+  L.end_outputs();
+  return P;
+}
+
+// ---------------------------------------------------------------------------
+// ba_solve_pose_batch
+// ---------------------------------------------------------------------------
+static inline void check_pose_batch(const char* fn, const ba_pose_batch* b, const double* cams_out) {
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what}; };
+  if (!b || b->n_problems < 0) throw invalid("bad batch");
+  const int n = b->n_problems;
+  if (n == 0) return;
+  if (!b->obs_offset || !b->cams || !b->K || !cams_out) throw invalid("null array");
+  check_offsets(fn, "obs_offset", b->obs_offset, n);
+  if (b->obs_offset[n] > 0 && (!b->pts || !b->obs_uv)) throw invalid("null array");
+}
+
+// The staging buffer, 16-B aligned sections: the batch | poses, summary records
+struct PoseLayout {
+  SectionLayout L{16};
+  size_t off = 0, cam = 0, K = 0, X = 0, uv = 0;
+  size_t out = 0, summ = 0;
+};
+static inline PoseLayout pose_layout(size_t N, size_t NO) {
+  PoseLayout P;
+  SectionLayout& L = P.L;
+  P.off = L.add(sizeof(int32_t) * (N + 1)); P.cam = L.add(sizeof(double) * 6 * N); P.K = L.add(sizeof(float) * 9 * N);
+  P.X = L.add(sizeof(double) * 3 * NO); P.uv = L.add(sizeof(float) * 2 * NO);
+  L.end_inputs();
+  P.out = L.add(sizeof(double) * 6 * N); P.summ = L.add(sizeof(double) * 8 * N);
+  L.end_outputs();
+  return P;
+}
+
+// ---------------------------------------------------------------------------
+// ba_triangulate
+// ---------------------------------------------------------------------------
+constexpr int kTriRec = 64;        // doubles per camera of the scratch: value-only record [0, 48), K-folded table [48, 64)
+
+static inline void tri_defaults(ba_tri_options& o) {
+  o.init = BA_TRI_INIT_DLT; o.refine = 0; o.min_views = 2;
+  o.checks = BA_TRI_CHECK_CHEIRALITY | BA_TRI_CHECK_CHI2 | BA_TRI_CHECK_SCALE;
+  o.behind_rule = 0; o.reserved = 0;
+}
+
+// Everything the kernels index with or branch on, checked on the host: the
+// options (returned with the defaults applied), with refine the resolved LM
+// options, then the batch and the output arrays.
+static inline ba_tri_options check_triangulate(const char* fn, const ba_tri_batch* b, const ba_tri_options* topt, const ba_options& lm,
+                                        const double* pts_out, const uint8_t* status) {
+  auto invalid = [&](const std::string& what) { return BaError{BA_ERR_INVALID_ARGUMENT, std::string(fn) + what}; };
+  if (!b || b->n_pts < 0 || b->n_cams < 0) throw invalid("bad batch");
+  ba_tri_options t;
+  if (topt) t = *topt; else tri_defaults(t);
+  if (t.init != BA_TRI_INIT_DLT && t.init != BA_TRI_INIT_GIVEN) throw invalid("unknown init " + std::to_string(t.init));
+  if (t.refine != 0 && t.refine != 1) throw invalid("unknown refine " + std::to_string(t.refine));
+  if (t.behind_rule != 0 && t.behind_rule != 1) throw invalid("unknown behind_rule " + std::to_string(t.behind_rule));
+  const int all_checks = BA_TRI_CHECK_CHEIRALITY | BA_TRI_CHECK_CHI2 | BA_TRI_CHECK_SCALE;
+  if (t.checks & ~all_checks) throw invalid("unknown checks bits " + std::to_string(t.checks));
+  if (t.min_views < 0) throw invalid("min_views " + std::to_string(t.min_views) + " is negative");
+  if (t.refine) {
+    if (lm.linear_solver != BA_DENSE_SCHUR) throw invalid("linear_solver must be BA_DENSE_SCHUR");
+    if (lm.precision != BA_FP64) throw invalid("precision must be BA_FP64");
+  }
+  const int np = b->n_pts, nc = b->n_cams;
+  if (np == 0) return t;
+  if (!b->obs_offset) throw invalid("null obs_offset");
+  if (!pts_out || !status) throw invalid("null output array");
+  check_offsets(fn, "obs_offset", b->obs_offset, np, "point");
+  const size_t no = (size_t)b->obs_offset[np];
+  if (no > 0 && (!b->obs_cam || !b->obs_uv)) throw invalid("null observation array");
+  if (nc > 0 && (!b->extr || !b->K)) throw invalid("null camera array (extr, K)");
+  if (nc > (int)(0x7fffffff / kTriRec)) throw invalid("too many cameras");
+  if (t.init == BA_TRI_INIT_GIVEN && !b->pts_init) throw invalid("init is BA_TRI_INIT_GIVEN but pts_init is null");
+  if ((t.checks & BA_TRI_CHECK_SCALE) && no > 0 && !b->cam_center) throw invalid("the scale test is on but cam_center is null");
+  for (size_t k = 0; k < no; ++k)
+    if (b->obs_cam[k] < 0 || b->obs_cam[k] >= nc)
+      throw invalid("obs_cam[" + std::to_string(k) + "] = " + std::to_string(b->obs_cam[k]) + " out of range (" +
+                    std::to_string(nc) + " cameras)");
+  return t;
+}
+
+// The staging buffer: cameras, offsets, observations, the optional scales and
+// initial points | points, summary records, status | the camera records
+struct TriLayout {
+  SectionLayout L{256};
+  size_t extr = 0, ctr = 0, K = 0, off = 0, oc = 0, uv = 0, sc = 0, init = 0;
+  size_t pts = 0, summ = 0, st = 0;
+  size_t rec = 0;
+};
+static inline TriLayout tri_layout(size_t nc, size_t np, size_t no, bool has_ctr, bool has_scale, bool given) {
+  TriLayout P;
+  SectionLayout& L = P.L;
+  P.extr = L.add(sizeof(float) * 16 * nc); P.ctr = L.add(has_ctr ? sizeof(float) * 3 * nc : 0);
+  P.K = L.add(sizeof(float) * 9 * nc); P.off = L.add(sizeof(int32_t) * (np + 1)); P.oc = L.add(sizeof(int32_t) * no);
+  P.uv = L.add(sizeof(float) * 2 * no); P.sc = L.add(has_scale ? sizeof(float) * no : 0);
+  P.init = L.add(given ? sizeof(double) * 3 * np : 0);
+  L.end_inputs();
+  P.pts = L.add(sizeof(double) * 3 * np); P.summ = L.add(sizeof(double) * 6 * np); P.st = L.add(np);
+  L.end_outputs();
+  P.rec = L.add(sizeof(double) * kTriRec * nc);
+  return P;
 }
 
 // ---------------------------------------------------------------------------
@@ -573,6 +729,34 @@ inline int map_graph_chunk(const ba_graph_options& p, const ba_map_table* t, int
   return (int)std::max<size_t>(1, std::min<size_t>(fit, (size_t)std::max(n_query, 1)));
 }
 
+// The staging buffer: the table (from the caller's arrays), its frame-sorted
+// view and the queries | the records, the point status | the scratch of `chunk`
+// queries (map_graph_query_bytes lists it) and their list offsets.
+struct MapGraphLayout {
+  SectionLayout L{256};
+  size_t frame_id = 0, is_key = 0, pt_invalid = 0, pt_ref = 0, off = 0, frame = 0, octave = 0, outlier = 0, obs_pt = 0,
+         perm = 0, frame_off = 0, query = 0;
+  size_t rec = 0, status = 0;
+  size_t W = 0, lst_f = 0, lst_w = 0, best = 0, loc = 0, fix = 0, pre = 0, ptb = 0, offs = 0;
+};
+static inline MapGraphLayout map_graph_layout(const ba_map_table* t, const ba_graph_options& p, int n_query, int chunk, bool want_status) {
+  MapGraphLayout P;
+  SectionLayout& L = P.L;
+  const size_t nf = (size_t)t->n_frames, np = (size_t)t->n_pts, no = (size_t)t->n_obs, nq = (size_t)n_query,
+               fw = map_graph_words(t->n_frames), pw = p.build_windows ? map_graph_words(t->n_pts) : 0, nc = (size_t)chunk;
+  P.frame_id = L.add(4 * nf); P.is_key = L.add(t->frame_is_key ? nf : 0); P.pt_invalid = L.add(t->pt_invalid ? np : 0);
+  P.pt_ref = L.add(want_status ? 4 * np : 0); P.off = L.add(4 * (np + 1)); P.frame = L.add(4 * no);
+  P.octave = L.add(t->obs_octave ? 4 * no : 0); P.outlier = L.add(t->obs_outlier ? no : 0); P.obs_pt = L.add(4 * no);
+  P.perm = L.add(4 * no); P.frame_off = L.add(4 * (nf + 1)); P.query = L.add(4 * nq);
+  L.end_inputs();
+  P.rec = L.add(sizeof(ba_graph_frame) * nq); P.status = L.add(want_status ? np : 0);
+  L.end_outputs();
+  P.W = L.add(4 * nc * nf); P.lst_f = L.add(4 * nc * nf); P.lst_w = L.add(4 * nc * nf);
+  P.best = L.add(4 * nc * BA_WINDOW_MAX_CAMS); P.loc = L.add(4 * nc * fw); P.fix = L.add(4 * nc * fw);
+  P.pre = L.add(4 * nc * fw); P.ptb = L.add(4 * nc * pw); P.offs = L.add(sizeof(long long) * 4 * nc);
+  return P;
+}
+
 // The plain restatement of ba_map_graph, query by query, on one thread: what
 // the kernels of ba_map_graph.hip compute (tests/cpp/map_graph_host.cpp runs it
 // under ASan + UBSan; tools/map_graph_bench.py times it).
@@ -975,7 +1159,9 @@ static inline WindowPack pack_window_structure(const ba_window_batch& b) {
     // observations by (point, camera), stable
     order.resize(q.no);
     for (int k = 0; k < q.no; ++k) order[k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+    // (the two pointers by value: by reference the comparator reloads them through the closure, and how
+    // well the compiler sees through that depends on what it inlines around this function: 2 ms per 256 windows)
+    std::stable_sort(order.begin(), order.end(), [op, oc](int x, int y) {
       return op[x] != op[y] ? op[x] < op[y] : oc[x] < oc[y];
     });
     q.poff0 = q.pt0 + i;
@@ -1006,6 +1192,47 @@ static inline WindowPack pack_window_structure(const ba_window_batch& b) {
   }
   return WindowPack{std::move(prob),    std::move(cam_vc),  std::move(pt_off), std::move(obs_cam), std::move(obs_slot),
                     std::move(cam_off), std::move(cam_obs), std::move(pt_var), std::move(uv),      NV};
+}
+
+// ba_iteration records per problem: one per iteration and the initial one;
+// refused when the logs of the batch would pass 2^40 bytes
+static inline size_t window_log_cap(const char* fn, int max_num_iterations, int n_problems) {
+  const size_t log_cap = (size_t)std::max(max_num_iterations, 0) + 1;
+  if (log_cap > (size_t(1) << 40) / (sizeof(ba_iteration) * (size_t)n_problems))
+    throw BaError{BA_ERR_OUT_OF_MEMORY, std::string(fn) + "the iteration logs do not fit (max_num_iterations x n_problems)"};
+  return log_cap;
+}
+
+// doubles per camera table row, value-only camera record and observation
+// record of the scratch (= kTblRec, kRecL, kJR of the device headers)
+constexpr int kWinTbl = 42, kWinVRec = 48, kWinJR = 20;
+
+// The staging buffer: the problems, parameters and structure | parameters,
+// summary records, iteration logs | the kernel's scratch (WinArgs documents it)
+struct WindowLayout {
+  SectionLayout L{256};
+  size_t prob = 0, cams = 0, pts = 0, K = 0, extr = 0, vc = 0, pv = 0, poff = 0, oc = 0, slot = 0, uv = 0, coff = 0, cobs = 0;
+  size_t cams_out = 0, pts_out = 0, summ = 0, log = 0;
+  size_t w_pts = 0, w_ctab = 0, w_vrec = 0, w_JR = 0, w_Hp = 0, w_sp = 0, w_prec = 0, w_W = 0, w_hc = 0;
+};
+static inline WindowLayout window_layout(const WindowPack& w, size_t log_cap) {
+  WindowLayout P;
+  SectionLayout& L = P.L;
+  const size_t n = w.prob.size(), NC = w.cam_vc.size(), NP = w.pt_var.size(), NO = w.obs_cam.size(), NV = w.NV;
+  P.prob = L.add(sizeof(WinProb) * n); P.cams = L.add(sizeof(double) * 6 * NC); P.pts = L.add(sizeof(double) * 3 * NP);
+  P.K = L.add(sizeof(float) * 9 * NC); P.extr = L.add(sizeof(float) * 16 * NC); P.vc = L.add(sizeof(int) * NC);
+  P.pv = L.add(NP); P.poff = L.add(sizeof(int) * (NP + n)); P.oc = L.add(sizeof(int) * NO); P.slot = L.add(sizeof(int) * NO);
+  P.uv = L.add(sizeof(float) * 2 * NO); P.coff = L.add(sizeof(int) * w.cam_off.size());
+  P.cobs = L.add(sizeof(int) * w.cam_obs.size());
+  L.end_inputs();
+  P.cams_out = L.add(sizeof(double) * 6 * NC); P.pts_out = L.add(sizeof(double) * 3 * NP);
+  P.summ = L.add(sizeof(double) * 8 * n); P.log = L.add(sizeof(ba_iteration) * log_cap * n);
+  L.end_outputs();
+  P.w_pts = L.add(sizeof(double) * 6 * NP); P.w_ctab = L.add(sizeof(double) * 2 * kWinTbl * NC);
+  P.w_vrec = L.add(sizeof(double) * kWinVRec * NC); P.w_JR = L.add(sizeof(double) * 2 * kWinJR * NO);
+  P.w_Hp = L.add(sizeof(double) * 18 * NP); P.w_sp = L.add(sizeof(double) * 3 * NP);
+  P.w_prec = L.add(sizeof(double) * 9 * NP); P.w_W = L.add(sizeof(double) * 18 * NO); P.w_hc = L.add(sizeof(double) * 54 * NV);
+  return P;
 }
 
 }  // namespace bahip

@@ -151,6 +151,23 @@ class Solver:
         if st != N.BA_OK:
             raise N.BAError(st, f"{what}: {self.lib.ba_last_error(self.h).decode(errors='replace')}")
 
+    def _times(self, getter) -> np.ndarray:
+        """What a ba_*_times getter holds (ms), as an array."""
+        n = getter(self.h, None, 0)
+        out = np.empty(max(n, 0))
+        if n > 0:
+            getter(self.h, _ptr(out), n)
+        return out
+
+    @staticmethod
+    def _set_options(p, options: dict, fields: dict, who: str):
+        """Keyword options into the ctypes options struct p; fields: name -> conversion."""
+        for key, val in options.items():
+            if key not in fields:
+                raise TypeError(f"{who}: unknown option {key!r}")
+            setattr(p, key, fields[key](val))
+        return p
+
     # -- multi-GPU ------------------------------------------------------
     @staticmethod
     def unique_id() -> bytes:
@@ -402,11 +419,7 @@ class Solver:
     def covariance_times(self) -> np.ndarray:
         """Device time (ms) of the phases of the last covariance() / covariance_ex() call:
         linearisation + reduced system, factorisation, inverse, gathers."""
-        n = self.lib.ba_covariance_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_covariance_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_covariance_times)
 
     def prune(self, extr, cam_center, K, obs_cam, obs_X, obs_uv, obs_inv_sigma, obs_dist) -> np.ndarray:
         """pruneCorrespondences (Optimizer.cpp:6-79) on the device for a batch of
@@ -486,11 +499,7 @@ class Solver:
     def window_times(self) -> np.ndarray:
         """Times (ms) of the last solve_window_batch: host preparation (wall),
         the kernel (device), the whole call (wall)."""
-        n = self.lib.ba_window_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_window_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_window_times)
 
     def triangulate(self, extr, K, obs_offset, obs_cam, obs_uv, *, cam_center=None, obs_scale=None, pts_init=None,
                     refine: bool = False, options: Options | None = None, huber_a: float = HUBER_A,
@@ -548,11 +557,7 @@ class Solver:
     def triangulate_times(self) -> np.ndarray:
         """Times (ms) of the last triangulate: host preparation (wall), the
         kernels (device), the whole call (wall)."""
-        n = self.lib.ba_triangulate_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_triangulate_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_triangulate_times)
 
     # -- robust absolute pose ---------------------------------------------
     def _pnp_batch(self, obs_offset, cams, K, pts, obs_uv, huber_a, pnp_options):
@@ -568,10 +573,7 @@ class Solver:
                             obs_uv=_ptr(uv), huber_a=float(huber_a))
         p = N.ba_pnp_options()
         self.lib.ba_pnp_defaults(C.byref(p))
-        for key, val in pnp_options.items():
-            if key not in PNP_OPTION_FIELDS:
-                raise TypeError(f"pnp: unknown option {key!r}")
-            setattr(p, key, float(val) if key == "threshold_px" else int(val))
+        self._set_options(p, pnp_options, {f: float if f == "threshold_px" else int for f in PNP_OPTION_FIELDS}, "pnp")
         return b, p, n, uv.shape[0], (off, c, k, x, uv)
 
     def pnp_ransac(self, obs_offset, cams, K, pts, obs_uv, *, options: Options | None = None,
@@ -621,11 +623,7 @@ class Solver:
     def pnp_times(self) -> np.ndarray:
         """Times (ms) of the last pnp_ransac: host preparation (wall), the
         kernels (device), the whole call (wall)."""
-        n = self.lib.ba_pnp_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_pnp_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_pnp_times)
 
     # -- two-view relative pose -------------------------------------------
     def _two_view_batch(self, match_offset, K1, K2, uv1, uv2, tv_options):
@@ -707,11 +705,7 @@ class Solver:
     def two_view_times(self) -> np.ndarray:
         """Times (ms) of the last two_view_ransac: host preparation (wall), the
         kernels (device), the whole call (wall)."""
-        n = self.lib.ba_two_view_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_two_view_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_two_view_times)
 
     # -- descriptor matching ------------------------------------------------
     def _match_batch(self, batch: MatchBatch):
@@ -739,10 +733,7 @@ class Solver:
         b, _keep = self._match_batch(mb)
         p = N.ba_match_options()
         self.lib.ba_match_defaults(C.byref(p))
-        for key, val in match_options.items():
-            if key not in ("ratio", "unique", "max_distance"):
-                raise TypeError(f"match_descriptors: unknown option {key!r}")
-            setattr(p, key, int(val) if key == "unique" else float(val))
+        self._set_options(p, match_options, {"ratio": float, "unique": int, "max_distance": float}, "match_descriptors")
         cap = 0
         if mb.pairs.size and mb.set_offset.size > 1:      # (a bad index or offset is the library's to report)
             n = np.maximum(np.diff(mb.set_offset.astype(np.int64)), 0)
@@ -773,16 +764,14 @@ class Solver:
         """Times (ms) of the last match_descriptors: host preparation (wall),
         the kernels (device), the whole call (wall), then the kernels' phases:
         norms, the 2-NN contraction, merge / ratio / unique / compaction."""
-        n = self.lib.ba_match_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_match_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_match_times)
 
     # -- point-cloud ICP -------------------------------------------------------
+    _ICP_ROUTES = {"AUTO": N.ICP_ROUTE_AUTO, "GRID": N.ICP_ROUTE_GRID, "BRUTE": N.ICP_ROUTE_BRUTE}
     _ICP_OPTIONS = {"max_iterations": int, "max_corr_dist": float, "mse_abs_eps": float, "mse_rel_eps": float,
                     "transformation_eps": float, "min_correspondences": int, "with_scale": int,
-                    "fitness_max_range": float, "route": int, "cell": float}
+                    "fitness_max_range": float, "cell": float,
+                    "route": lambda v: Solver._ICP_ROUTES[v] if isinstance(v, str) else int(v)}
 
     def _icp_batch(self, ib: IcpBatch, icp_options: dict, who: str):
         ps = np.ascontiguousarray(ib.pairs[:, 0])
@@ -791,12 +780,7 @@ class Solver:
                            xyz=_ptr(ib.xyz), pair_src=_ptr(ps), pair_tgt=_ptr(pt), guess=_ptr(ib.guess))
         p = N.ba_icp_options()
         self.lib.ba_icp_defaults(C.byref(p))
-        for key, val in icp_options.items():
-            if key not in self._ICP_OPTIONS:
-                raise TypeError(f"{who}: unknown option {key!r}")
-            if key == "route" and isinstance(val, str):
-                val = {"AUTO": N.ICP_ROUTE_AUTO, "GRID": N.ICP_ROUTE_GRID, "BRUTE": N.ICP_ROUTE_BRUTE}[val]
-            setattr(p, key, self._ICP_OPTIONS[key](val))
+        self._set_options(p, icp_options, self._ICP_OPTIONS, who)
         return b, p, (ps, pt, ib)
 
     def icp(self, sets, pairs=None, guess=None, **icp_options) -> tuple[np.ndarray, np.ndarray]:
@@ -836,11 +820,7 @@ class Solver:
     def icp_times(self) -> np.ndarray:
         """Times (ms) of the last icp: host preparation (wall), the kernels
         (device), the whole call (wall), the kernels per enqueued round."""
-        n = self.lib.ba_icp_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_icp_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_icp_times)
 
     # -- map-point upkeep and association gates --------------------------------
     def _map_point_batch(self, mb: MapPointBatch):
@@ -858,10 +838,8 @@ class Solver:
         b = self._map_point_batch(batch)
         p = N.ba_map_point_options()
         self.lib.ba_map_points_defaults(C.byref(p))
-        for key, val in mp_options.items():
-            if key not in ("median_rule", "max_scale", "reserved", "reserved_f"):
-                raise TypeError(f"map_points_update: unknown option {key!r}")
-            setattr(p, key, float(val) if key in ("max_scale", "reserved_f") else int(val))
+        self._set_options(p, mp_options, {"median_rule": int, "max_scale": float, "reserved": int, "reserved_f": float},
+                          "map_points_update")
         n = batch.pts.shape[0]
         out = np.zeros(max(n, 1), MAP_POINT_DTYPE)
         desc_out = np.zeros((max(n, 1), int(batch.dim)), np.float32) if want_desc else None
@@ -885,11 +863,7 @@ class Solver:
     def map_points_times(self) -> np.ndarray:
         """Times (ms) of the last map_points_update: host preparation (wall),
         the kernels (device), the whole call (wall)."""
-        n = self.lib.ba_map_points_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_map_points_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_map_points_times)
 
     def associate(self, batch: AssocBatch, **assoc_options):
         """The gates of searchInNeighbors per candidate item and fuse pair
@@ -906,10 +880,8 @@ class Solver:
                              item_cur_row=_ptr(ab.item_cur_row), fuse_pairs=_ptr(ab.fuse_pairs))
         p = N.ba_assoc_options()
         self.lib.ba_associate_defaults(C.byref(p))
-        for key, val in assoc_options.items():
-            if key not in ("chi2", "min_cos", "max_desc_dist", "fuse_min_cos", "fuse_max_desc_dist", "reserved"):
-                raise TypeError(f"associate: unknown option {key!r}")
-            setattr(p, key, int(val) if key == "reserved" else float(val))
+        self._set_options(p, assoc_options, {"chi2": float, "min_cos": float, "max_desc_dist": float, "fuse_min_cos": float,
+                                             "fuse_max_desc_dist": float, "reserved": int}, "associate")
         ni, nf = ab.item_cam.shape[0], ab.fuse_pairs.shape[0]
         items = np.zeros(max(ni, 1), ASSOC_DTYPE)
         fuse = np.zeros(max(nf, 1), FUSE_DTYPE)
@@ -917,8 +889,8 @@ class Solver:
         return items[:ni].copy(), fuse[:nf].copy()
 
     # -- covisibility lists, culling votes, local-BA windows ---------------------
-    _GRAPH_OPTIONS = ("th", "n_best", "order", "build_windows", "current_frame_id", "debug_tile_frames",
-                      "debug_chunk_queries", "reserved", "redundant_fraction")
+    _GRAPH_OPTIONS = {"th": int, "n_best": int, "order": int, "build_windows": int, "current_frame_id": int,
+                      "debug_tile_frames": int, "debug_chunk_queries": int, "reserved": int, "redundant_fraction": float}
 
     def _map_table(self, table: MapTable):
         t = table.normalized()
@@ -930,11 +902,7 @@ class Solver:
     def _graph_options(self, fn: str, options: dict):
         p = N.ba_graph_options()
         self.lib.ba_map_graph_defaults(C.byref(p))
-        for key, val in options.items():
-            if key not in self._GRAPH_OPTIONS:
-                raise TypeError(f"{fn}: unknown option {key!r}")
-            setattr(p, key, float(val) if key == "redundant_fraction" else int(val))
-        return p
+        return self._set_options(p, options, self._GRAPH_OPTIONS, fn)
 
     def map_graph(self, table: MapTable, queries, pt_status: bool = False, lists: bool = True, **options) -> MapGraphResult:
         """Covisibility lists, culling votes and local-BA windows of the query
@@ -983,11 +951,7 @@ class Solver:
     def map_graph_times(self) -> np.ndarray:
         """Times (ms) of the last map_graph: host preparation (wall), the
         kernels (device), the whole call (wall)."""
-        n = self.lib.ba_map_graph_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_map_graph_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_map_graph_times)
 
     def synchronize(self):
         self._check(self.lib.ba_synchronize(self.h), "ba_synchronize")
@@ -1013,11 +977,7 @@ class Solver:
     def bench_iteration_times(self) -> np.ndarray:
         """Host wall time (ms) of each LM iteration of the last
         bench_iterations call (scalar record to scalar record)."""
-        n = self.lib.ba_bench_iteration_times(self.h, None, 0)
-        out = np.empty(max(n, 0))
-        if n > 0:
-            self.lib.ba_bench_iteration_times(self.h, _ptr(out), n)
-        return out
+        return self._times(self.lib.ba_bench_iteration_times)
 
     def stream_copy(self, nbytes: int = 1 << 30, reps: int = 10) -> float:
         """Measured device copy bandwidth in GB/s (read + write bytes), the

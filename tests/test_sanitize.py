@@ -11,7 +11,9 @@
     the BAL text reader;
   * batch_pack_san — the host-only packer of the batch entry points
     (host/ba_batch_pack.hpp): the structure build of ba_solve_window_batch on
-    well-formed and malformed batches, the section layout, check_offsets.
+    well-formed and malformed batches, the section layout, check_offsets, and
+    the validators and layout builders of ba_prune, ba_solve_pose_batch,
+    ba_triangulate, the window batch, the map graph and the inspection entries.
 Each must run clean (exit 0, no sanitizer report, leak check on) and produce
 the same result as the plain build.  GPU code cannot be sanitized on this
 pool; the device side is covered by the parity tests.
@@ -222,3 +224,48 @@ def test_batch_packer_under_asan_ubsan(san_build, tmp_path):
     refused(decreasing, "decreases", "problem 1")
     refused(seventeen, "problem 6", "17")
     refused(first_offset, "offset[0] != 0")
+
+
+# the validators of the other batch entry points: the accepted batch, then the
+# refusals that the GPU error tests provoke, with their exact messages
+ACCEPTED = ("prune", "pose", "tri", "tri_defaults", "tri_given_ok", "window_log", "hyp")
+REFUSED = {
+    "prune_sizes": "error 1: ba_prune: bad sizes",
+    "prune_null": "error 1: ba_prune: null array",
+    "prune_cam": "error 1: ba_prune: obs_cam[2] out of range",
+    "prune_negative": "error 1: ba_prune: obs_cam[4] out of range",
+    "pose_negative": "error 1: ba_solve_pose_batch: bad batch",
+    "pose_null": "error 1: ba_solve_pose_batch: null array",
+    "pose_out": "error 1: ba_solve_pose_batch: null array",
+    "pose_first": "error 1: ba_solve_pose_batch: obs_offset[0] != 0",
+    "pose_decreasing": "error 1: ba_solve_pose_batch: obs_offset decreases at problem 1",
+    "tri_init": "error 1: ba_triangulate: unknown init 7",
+    "tri_checks": "error 1: ba_triangulate: unknown checks bits 64",
+    "tri_views": "error 1: ba_triangulate: min_views -1 is negative",
+    "tri_solver": "error 1: ba_triangulate: linear_solver must be BA_DENSE_SCHUR",
+    "tri_precision": "error 1: ba_triangulate: precision must be BA_FP64",
+    "tri_out": "error 1: ba_triangulate: null output array",
+    "tri_decreasing": "error 1: ba_triangulate: obs_offset decreases at point 1",
+    "tri_given": "error 1: ba_triangulate: init is BA_TRI_INIT_GIVEN but pts_init is null",
+    "tri_scale": "error 1: ba_triangulate: the scale test is on but cam_center is null",
+    "tri_cam": "error 1: ba_triangulate: obs_cam[1] = 5 out of range (2 cameras)",
+    "window_log_overflow": "error 3: ba_solve_window_batch: the iteration logs do not fit (max_num_iterations x n_problems)",
+    "hyp_index": "error 1: fn: pair 3 out of range",
+    "hyp_negative": "error 1: fn: problem -1 out of range",
+    "hyp_range": "error 1: fn: hypotheses [5, 12) outside max_hypotheses 10",
+    "hyp_wrap": "error 1: fn: hypotheses [2147483647, 4294967294) outside max_hypotheses 10",
+}
+
+
+def test_batch_validators_and_layouts_under_asan_ubsan(san_build):
+    exe = san_build / "batch_pack_san"
+    for name in ACCEPTED:
+        assert run_clean([exe, "check", name]).splitlines()[-1] == "ok", name
+    for name, message in REFUSED.items():
+        assert run_clean([exe, "check", name], rc=3).splitlines()[-1] == message, name
+    out = run_clean([exe, "check", "layouts"]).splitlines()
+    assert out[-1] == "ok" and [line.split()[1].rstrip(":") for line in out[:-1]] == \
+        ["prune", "pose"] + ["tri"] * 8 + ["window"] + ["map_graph"] * 4
+    for line in out[:-1]:
+        in_b, io_b, total = (int(v) for v in line.split()[2:])
+        assert 0 < in_b < io_b <= total, line
